@@ -16,9 +16,11 @@ launches, inside the timed region: extra work, never less).  Trained on, the syn
 different work; ``--moving`` restores that behaviour, and the line carries the proposal stage's counts of the timed steps
 (``proposal_stage``) either way.
 
-Prints ONE JSON line on rank 0 with the contract fields plus ``roofline`` (dominant kernel, measured with hipEvents
-inside libgpn_hip.so during an extra instrumented step) and ``cpu_baseline`` (the same train step through the CPU
-oracle on a bounded sample; rank 0, N=1 only).
+Prints ONE JSON line on rank 0 with the contract fields.  A plain run sets up, warms up, times --steps steps and prints;
+``--full`` adds the secondary measurements: ``roofline`` (dominant kernel, measured with hipEvents inside libgpn_hip.so
+during an extra instrumented step), ``validation`` (validation steps, BASELINE config 2 shape) and ``cpu_baseline`` (the
+same train step through the CPU oracle on a bounded sample; rank 0, N=1 only).  ``--dump-outputs DIR`` writes what the
+last timed step computed (loss, gradients, sampled parameters and Adam moments) as .npy files.
 """
 import argparse
 import json
@@ -55,6 +57,11 @@ def parse():
     ap.add_argument("--moving", action="store_true",
                     help="let the parameters train on (rounds 1-5: the proposal stage's load then depends on how many steps preceded)")
     ap.add_argument("--cpu-scenes", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: the instrumented roofline step, the validation-step leg and the CPU "
+                         "baseline (--no-validation / --no-cpu-baseline still drop one of them); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -295,6 +302,33 @@ def validation_leg(args, device):
                         "median of three 18-step loops after one warm-up loop"}
 
 
+DUMP_SAMPLE = 1 << 20  # positions of the parameter-sized arrays sampled by dump_outputs (seeded: the same in every run)
+
+
+def dump_outputs(directory, model, optimizer, loss):
+    """--dump-outputs: what the timed train step returned to its caller in the last timed step, as .npy files (~44 MB) -
+    loss.npy (float64, [1]); grads.npy (float32: every trainable parameter's gradient in model.parameters() order, flattened
+    and concatenated, zeros where a parameter got none); and, at DUMP_SAMPLE positions of that same concatenation drawn with
+    a fixed seed, the parameter values after the step (params_sample.npy) and Adam's two moment estimates
+    (adam_exp_avg_sample.npy, adam_exp_avg_sq_sample.npy).  Inputs and weights are seeded, so two builds run with the same
+    arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+
+    def flat(tensors):
+        return torch.cat([t.detach().reshape(-1).to(torch.float32) for t in tensors]).cpu().numpy()
+
+    grads = flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
+    idx = np.sort(np.random.default_rng(0).choice(grads.size, size=min(grads.size, DUMP_SAMPLE), replace=False))
+    arrays = {"loss": np.array([float(loss.detach())], np.float64), "grads": grads, "params_sample": flat(params)[idx]}
+    for key in ("exp_avg", "exp_avg_sq"):
+        moments = [optimizer.state[p][key] if key in optimizer.state.get(p, {}) else torch.zeros_like(p) for p in params]
+        arrays[f"adam_{key}_sample"] = flat(moments)[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def apply_lib_knobs(spec: str):
     """--lib-knobs name=value,...: the library's measurement switches (include/gpn.h), all of them entry points"""
     import ctypes
@@ -428,7 +462,7 @@ def main():
     cpu0 = time.process_time()  # CPU seconds of every thread of this process (main, weight-gradient helper, runtime threads)
     plans = []  # the proposal stage's counts as the host learns them (two steps late, never waited for): a list append per step
     for i in range(args.steps):
-        step(next(feed), i)
+        loss = step(next(feed), i)
         plans.append(model._prop_hist[-1] if getattr(model, "_prop_hist", None) else None)
     torch.cuda.synchronize(device)
     if world > 1:
@@ -440,10 +474,12 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, optimizer, loss)
 
-    # instrumented extra step (not timed): hipEvent pairs around the conv kernels on their launch stream
+    # --full: instrumented extra step (not timed): hipEvent pairs around the conv kernels on their launch stream
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         lib = _C.lib()
         lib.gpn_prof_reset(); lib.gpn_prof_enable(1)
         GF.CONV_LOG = []
@@ -508,7 +544,7 @@ def main():
                         all_kernels={v["kernel"]: family(v) for v in prof.values()},
                         # per conv shape: which roofline binds (flop/B against the machine balance) and how far from it
                         levels=levels)
-    elif world > 1:
+    elif args.full and world > 1:
         step(next(feed), 0)  # keep ranks in lock-step through the extra step's gradient exchange
     if world > 1:
         dist.barrier()
@@ -541,12 +577,12 @@ def main():
             out["distributed"] = {"world_size": dist.get_world_size(), "rank_reporting": dist.get_rank(),
                                   "backend": dist.get_backend(), "env_world_size": int(os.environ.get("WORLD_SIZE", "1")),
                                   "device": torch.cuda.get_device_name(device)}
-        if world == 1 and not args.no_validation:
+        if args.full and world == 1 and not args.no_validation:
             try:  # (a secondary figure: it must never cost the run its headline)
                 out["validation"] = validation_leg(args, device)
             except Exception as exc:  # noqa: BLE001
                 out["validation"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -56,3 +56,42 @@ def test_proposal_summary():
     assert bench.proposal_summary([None, None]) is None
     s = bench.proposal_summary([None, [100, 18002, 487, 11211, 0, 0, 300], [90, 17000, 480, 11000, 0, 0, 290]])
     assert s["points_per_step"] == [18002, 17000] and s["proposals_min_max"] == [480, 487]
+
+
+def test_secondary_measurements_are_off_unless_full(monkeypatch):
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "5", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 5 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs: float arrays only, under 64 MB in all, the same sample positions in every run"""
+    import numpy as np
+    import torch
+    bench = _bench()
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(300, 400), torch.nn.Linear(400, 3))
+    model[1].bias.requires_grad_(False)
+    opt = torch.optim.Adam(model.parameters())
+    loss = model(torch.randn(5, 300)).square().mean()
+    loss.backward()
+    opt.step()
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), model, opt, loss)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["adam_exp_avg_sample.npy", "adam_exp_avg_sq_sample.npy", "grads.npy", "loss.npy", "params_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["loss.npy"].dtype == np.float64 and got["loss.npy"][0] == float(loss.detach())
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    want = torch.cat([p.grad.reshape(-1) for p in trainable]).numpy()
+    assert np.array_equal(got["grads.npy"], want)
+    n = min(want.size, bench.DUMP_SAMPLE)
+    assert got["params_sample.npy"].shape == (n,) and got["adam_exp_avg_sq_sample.npy"].shape == (n,)
+    for f in files:
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f))

@@ -476,7 +476,7 @@ def test_two_rank_bench_shares_one_device(cuda, launcher):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     bench = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--points", "6000",
-             "--no-cpu-baseline"]
+             "--no-cpu-baseline", "--full"]  # (--full: the instrumented extra step is one of the four exchanges counted below)
     if launcher == "self":
         cmd = [sys.executable] + bench
     else:
@@ -507,7 +507,8 @@ def test_bench_with_the_gradient_exchange_forced_on_one_rank(cuda):
     env = dict(os.environ, GPN_BENCH_FORCE_GRAD_SYNC="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--points", "6000", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--points", "6000", "--no-cpu-baseline",
+           "--full"]  # (--full: the instrumented extra step is one of the five exchanges counted below)
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

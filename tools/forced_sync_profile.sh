@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-GPN_BENCH_FORCE_GRAD_SYNC=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf -o t -- python $R/bench.py --steps 16 --warmup 4 --no-cpu-baseline > /tmp/fs.log 2>&1
+GPN_BENCH_FORCE_GRAD_SYNC=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/pf" -o t -- python $R/bench.py --full --steps 16 --warmup 4 --no-cpu-baseline > "$TMPDIR/fs.log" 2>&1
 tail -1 /tmp/fs.log | cut -c1-200
 f=$(find /tmp/pf -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'P'

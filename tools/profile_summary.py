@@ -35,7 +35,7 @@ def main():
             fam[k][0] += t
             fam[k][1] += c
     rec = {"kernel_source_fingerprint": kernel_source_fingerprint(), "steps_traced": steps,
-           "command": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 16 --warmup 4 --no-cpu-baseline --no-validation",
+           "command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline --no-validation",
            "families": {k: {"ms_per_step": v[0] / 1e6 / steps, "launches_per_step": v[1] / steps} for k, v in fam.items()},
            "all_kernels": {"ms_per_step": total[0] / 1e6 / steps, "launches_per_step": total[1] / steps}}
     with open(out_path, "w") as fh:

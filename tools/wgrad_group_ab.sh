@@ -10,7 +10,7 @@ N=${1:-4}
 cd "$R"
 GPN_WGRAD_GROUP=4 timeout 600 python -m pytest tests -m gpu -q -x -k "executor or pair or golden or train_step or determin or wgrad" 2>&1 < /dev/null | tail -2
 export TMPDIR=/tmp
-(cd /tmp && rm -rf /tmp/pg && GPN_WGRAD_GROUP=4 timeout 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/pg -o t -- python "$R/bench.py" --steps 16 --warmup 4 --no-cpu-baseline > /dev/null 2>&1 < /dev/null)
+(cd "$TMPDIR" && rm -rf "$TMPDIR/pg" && GPN_WGRAD_GROUP=4 timeout 200 rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/pg" -o t -- python "$R/bench.py" --full --steps 16 --warmup 4 --no-cpu-baseline > /dev/null 2>&1 < /dev/null)
 f=$(find /tmp/pg -name "*kernel_trace.csv" 2>/dev/null | head -1)
 if [ -n "$f" ]; then python tools/queue_breakdown.py "$f" 21 2>/dev/null | grep "^queue"; fi
 run() { env "$@" timeout 200 python bench.py --steps 60 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$*', round(d['ms_per_step'],3))"; }
