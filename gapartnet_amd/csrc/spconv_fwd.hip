@@ -249,14 +249,12 @@ int launch_fwd(const FwdPlan& p, const float* in, const float* packed, const int
 template <int NTW, int CW>
 int dispatch_ns(const FwdPlan& p, const float* in, const float* packed, const int32_t* nbr, int K, int64_t n_dst,
                 int cin, int nt_total, int accumulate, float* out, hipStream_t stream) {
-  constexpr int SLAB_V4 = FwdCfg<NTW, CW>::SLAB_V4;
-  const int ns = (int)gpn::cdiv(SLAB_V4, p.wpb * 64);
-  switch (ns) {
-    case 1: return launch_fwd<NTW, CW, 1>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-    case 2: return launch_fwd<NTW, CW, 2>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-    case 3: return launch_fwd<NTW, CW, 3>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-    default: return launch_fwd<NTW, CW, 4>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-  }
+  // NS = ceil(CW NTW / waves per workgroup) and plan_fwd gives 4, 8 or 16 waves: only those three values are instantiated
+  constexpr int X = CW * NTW, NS4 = (X + 3) / 4, NS8 = (X + 7) / 8, NS16 = (X + 15) / 16;
+  const int ns = (int)gpn::cdiv(X, p.wpb);
+  if (ns == NS4) return launch_fwd<NTW, CW, NS4>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
+  if (ns == NS8) return launch_fwd<NTW, CW, NS8>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
+  return launch_fwd<NTW, CW, NS16>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
 }
 
 template <int NTW>

@@ -494,6 +494,7 @@ def rulebook_down_dev(indices, spatial_shape, batch_size, rows: DevCount, batch:
 
 # ---------------------------------------------------------------------------------------------------- C
 LAYOUT_OKI = 4
+WGRAD_MAX_COUT = 128  # widest dout gpn_spconv_wgrad contracts in one call
 
 
 def _wdims(W, layout):
@@ -610,6 +611,22 @@ def conv_wgrad(features, dout, rb: Rulebook, layout="kio"):
         _dev(features, dout)
     cin, cout = features.shape[1], dout.shape[1]
     shape = (cout, rb.K, cin) if layout == "oki" else (rb.K, cin, cout)
+    if cout > WGRAD_MAX_COUT:
+        # the contraction takes at most 128 output columns (gpn_spconv_wgrad, include/gpn.h): balanced pieces of <= 128 columns
+        # of dout, each piece's gradient copied into its columns ("kio") / rows ("oki") of dW
+        nt = cout // 16
+        n = -(-nt // (WGRAD_MAX_COUT // 16))
+        dW = torch.empty(shape, dtype=torch.float32, device=features.device)
+        c0 = 0
+        for i in range(n):
+            c1 = c0 + 16 * (nt // n + (1 if i < nt % n else 0))
+            piece = conv_wgrad(features, dout[:, c0:c1].contiguous(), rb, layout)
+            if layout == "oki":
+                dW[c0:c1].copy_(piece)
+            else:
+                dW[:, :, c0:c1].copy_(piece)
+            c0 = c1
+        return dW
     dW = torch.empty(shape, dtype=torch.float32, device=features.device)
     L = _C.lib()
     ws_ptr, ws_size, stream = _fast_ws(features.device, 0)

@@ -194,6 +194,7 @@ int gpn_rulebook_down_lists(const int32_t* fine_to_coarse, const int32_t* tap, i
  * gpn_spconv_fwd: out[dst] = sum_k in[nbr[k][dst]] @ W_k over the tap-major neighbour table of a rulebook
  *   (nbr [K, n_dst] i32, -1 = no neighbour; out is fully overwritten).  in [n_src, cin], out [n_dst, cout].
  * gpn_spconv_wgrad: dW[k] = sum_{pairs of k} in[src]^T (x) dout[dst]  -> dW [K, cin, cout] canonical.
+ *   cout <= 128 (GPN_ERR_ARG above: callers split dout into <= 128-column pieces, as hip_ops.conv_wgrad does); any cin.
  * ================================================================================================ */
 #define GPN_PACK_TRANSPOSE 1
 #define GPN_PACK_REVERSE 2
