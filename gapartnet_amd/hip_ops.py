@@ -1288,3 +1288,108 @@ def score_loss(logits, cls_source, proposal_offsets, ious, fg_thresh, bg_thresh,
                                   ptr(po), ptr(ious), i32(ious.shape[1]), i64(P), f32(fg_thresh), f32(bg_thresh), ptr(loss),
                                   ptr(preds), ptr(d_logits), _stream()), "gpn_score_loss")
     return loss, preds, d_logits
+
+
+# ---------------------------------------------------------------------------------------------------- VP (rendered views)
+VIEW_OK, VIEW_TOO_FEW, VIEW_LABEL_MISMATCH, VIEW_INSTANCE_BOUND = 0, 1, 2, 3
+
+
+def view_max_instance_ids() -> int:
+    return int(_C.lib().gpn_view_max_instance_ids())
+
+
+def view_backproject(depth, sem, ins, K, status=None):
+    """depth [V,H,W] f32 / f64, sem / ins [V,H,W] i32, K [V,3,3] f64 -> (pixel [V,H*W] i32 = the valid pixels' linear indices in
+    row-major order, points [V,H*W,4] f32 = the float32 cast of their float64 back-projection in .xyz, counts [V] i32,
+    status [V] i32), all left on the device"""
+    dev = _dev(depth, sem, ins, K)
+    if depth.dtype not in (torch.float32, torch.float64):
+        raise _C.GpnError(f"view depth must be float32 or float64, got {depth.dtype}")
+    depth = depth.contiguous()
+    sem, ins, K = _c(sem, torch.int32), _c(ins, torch.int32), _c(K, torch.float64)
+    V, H, W = depth.shape
+    pixel = torch.empty((V, H * W), dtype=torch.int32, device=dev)
+    points = torch.empty((V, H * W, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((V,), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty((V,), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_view_backproject(ptr(depth), i32(depth.element_size()), ptr(sem), ptr(ins), ptr(K), i32(V), i32(H), i32(W),
+                                        ptr(pixel), ptr(points), ptr(counts), ptr(status), _stream()), "gpn_view_backproject")
+    return pixel, points, counts, status
+
+
+def view_fps(points, counts, status, m, max_groups=0):
+    """ragged FPS of all V views in one launch: for each view with status VIEW_OK the m samples gpn_pn2_furthest_point_sampling
+    takes from points[v, :counts[v], :3] alone (counts[v] == m: arange; < m: status VIEW_TOO_FEW).  points [V, n_bound, 4] f32
+    (.w is overwritten).  max_groups > 0 caps the workgroups per view (1: the form without inter-workgroup waits)."""
+    dev = _dev(points, counts, status)
+    V, nb, _ = points.shape
+    idx = torch.zeros((V, int(m)), dtype=torch.int32, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_view_fps_ws_bytes(i32(V)), dev)
+    check(L.gpn_view_fps(ptr(points), i64(nb), ptr(counts), ptr(status), i32(V), i32(m), i32(max_groups), ptr(idx), ptr(ws),
+                         szt(ws.numel()), _stream()), "gpn_view_fps")
+    return idx
+
+
+def view_fps_ragged(xyz, counts, m, max_groups=0):
+    """view_fps over clouds given as xyz [V, n_max, 3] f32 with counts [V] live rows -> (idx [V, m] i32, status [V] i32)"""
+    dev = _dev(xyz, counts)
+    V, nb, _ = xyz.shape
+    points = torch.zeros((V, nb, 4), dtype=torch.float32, device=dev)
+    points[..., :3] = xyz
+    status = torch.zeros((V,), dtype=torch.int32, device=dev)
+    idx = view_fps(points, _c(counts, torch.int32), status, m, max_groups)
+    return idx, status
+
+
+_VIEW_FIELDS = (("xyz", torch.float32, 3), ("rgb", torch.float32, 3), ("sem", torch.int32, 0), ("ins", torch.int32, 0),
+                ("npcs", torch.float32, 3), ("pix", torch.int32, 2), ("gt", torch.int32, 0))
+
+
+def view_layout(V, m):
+    """(name, dtype, shape, byte offset) of every result of view_convert inside its one buffer, and the buffer's size"""
+    fields = [("scale", torch.float64, (V, 4)), ("status", torch.int32, (V,))]
+    fields += [(name, dt, (V, m, c) if c else (V, m)) for name, dt, c in _VIEW_FIELDS]
+    layout, total = [], 0
+    for name, dt, shape in fields:
+        layout.append((name, dt, shape, total))
+        total += (int(np.prod(shape)) * (8 if dt == torch.float64 else 4) + 255) // 256 * 256
+    return layout, total
+
+
+def view_fields(buf, layout):
+    """views of a view_convert buffer (on the device or a host copy of it) by name"""
+    out = {}
+    for name, dt, shape, off in layout:
+        nbytes = int(np.prod(shape)) * (8 if dt == torch.float64 else 4)
+        out[name] = buf[off:off + nbytes].view(dt).view(shape)
+    return out
+
+
+def view_convert(depth, rgb, sem, ins, npcs, K, m, max_groups=0):
+    """rendered views -> training scenes for V views of one size (the three launches of include/gpn.h section VP, no host read
+    in between).  depth [V,H,W] f32 / f64, rgb [V,H,W,3] u8, sem / ins [V,H,W] i32, npcs [V,H,W,3] f32, K [V,3,3] f64.
+    -> (buffer, layout): every result in ONE device buffer, so that a batch costs one host read (view_fields names them:
+    scale [V,4] f64, status [V] i32, xyz / rgb / npcs [V,m,3] f32, sem / ins / gt [V,m] i32, pix [V,m,2] i32)."""
+    dev = _dev(depth, rgb, sem, ins, npcs, K)
+    if depth.dtype not in (torch.float32, torch.float64):
+        raise _C.GpnError(f"view depth must be float32 or float64, got {depth.dtype}")
+    V, H, W = depth.shape
+    m = int(m)
+    depth = depth.contiguous()
+    rgb, npcs = _c(rgb, torch.uint8), _c(npcs, torch.float32)
+    sem, ins, K = _c(sem, torch.int32), _c(ins, torch.int32), _c(K, torch.float64)
+    if tuple(rgb.shape) != (V, H, W, 3) or tuple(npcs.shape) != (V, H, W, 3) or tuple(sem.shape) != (V, H, W) \
+            or tuple(ins.shape) != (V, H, W) or K.numel() != V * 9:
+        raise _C.GpnError("view_convert: rgb / npcs must be [V,H,W,3], sem / ins [V,H,W], K [V,3,3]")
+    layout, total = view_layout(V, m)
+    buf = torch.empty((total,), dtype=torch.uint8, device=dev)
+    f = view_fields(buf, layout)
+    pixel, points, counts, _ = view_backproject(depth, sem, ins, K, status=f["status"])
+    idx = view_fps(points, counts, f["status"], m, max_groups)
+    check(_C.lib().gpn_view_finish(ptr(depth), i32(depth.element_size()), ptr(rgb), ptr(sem), ptr(ins), ptr(npcs), ptr(K), i32(V),
+                                   i32(H), i32(W), ptr(pixel), ptr(idx), i32(m), ptr(f["status"]), ptr(f["xyz"]), ptr(f["rgb"]),
+                                   ptr(f["sem"]), ptr(f["ins"]), ptr(f["npcs"]), ptr(f["pix"]), ptr(f["gt"]), ptr(f["scale"]),
+                                   _stream()), "gpn_view_finish")
+    return buf, layout

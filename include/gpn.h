@@ -672,6 +672,41 @@ int gpn_adam_step_gated(const gpn_adam_tensor_t* table_dev, const int32_t* block
                         int64_t* skipped_dev, gpn_stream_t stream);
 
 /* ================================================================================================
+ * VP - rendered RGB-D views -> training scenes (the reference's dataset/process_tools/convert_rendered_into_input.py,
+ * sample_and_save :90-175) for a batch of V views of one size H x W, in three launches with no host read between them.
+ * Inputs per view: depth [H,W] f32 (depth_bytes 4) or f64 (8), sem / ins [H,W] i32 (-2 background, -1 "others"), rgb [H,W,3] u8,
+ * npcs [H,W,3] f32, K [3,3] f64 row-major (meta['camera_intrinsic'] reshaped, :44).
+ * gpn_view_backproject: valid pixels (sem != -2 and ins != -2, :55) in row-major order -> pixel [V, H*W] i32 (linear index),
+ *   points [V, H*W, 4] f32 = the float32 cast of the float64 ((pix - c) * z) / f back-projection (:57-59) in .xyz, .w scratch;
+ *   counts [V] i32 and status [V] i32 (GPN_VIEW_OK or GPN_VIEW_LABEL_MISMATCH, where the reference asserts, :112) on the device.
+ * gpn_view_fps: per view with status OK, idx [V, m] i32 = gpn_pn2_furthest_point_sampling of that view's counts[v] points alone
+ *   (utils/sample_utils.py:46-66: start 0, ties as the reference's block reduction for opt_n_threads(n)); counts[v] == m: arange;
+ *   counts[v] < m: status GPN_VIEW_TOO_FEW (:116-117).  points [V, n_bound, 4] as above (.w is overwritten).  All views in one
+ *   launch; several workgroups share a view and meet at a counter only under a cooperative launch whose grid is at most one
+ *   workgroup per CU, otherwise one workgroup per view without any wait.  max_groups > 0 caps the workgroups per view (1: the
+ *   wait-free form).
+ * gpn_view_finish: per view with status OK, from the original maps: xyz [V,m,3] f32 = ball-normalised float64 points (:71-87,
+ *   center (max + min) / 2, r = sqrt(max((dx^2 + dy^2) + dz^2))), rgb [V,m,3] f32 = u8 / 255.0, sem [V,m] = sem + 1, ins [V,m] =
+ *   -1 -> -100 then the relabel loop (:142-147), npcs [V,m,3], pix [V,m,2] = (y, x), gt [V,m] = sem of the instance's first point
+ *   * 1000 + id, -100 elsewhere (:162-171), scale [V,4] f64 = (r, cx, cy, cz).  A sampled instance id >=
+ *   gpn_view_max_instance_ids() sets status GPN_VIEW_INSTANCE_BOUND (that view's outputs are not to be used).
+ * ================================================================================================ */
+#define GPN_VIEW_OK 0
+#define GPN_VIEW_TOO_FEW 1
+#define GPN_VIEW_LABEL_MISMATCH 2
+#define GPN_VIEW_INSTANCE_BOUND 3
+int gpn_view_max_instance_ids(void);
+int gpn_view_backproject(const void* depth, int depth_bytes, const int32_t* sem, const int32_t* ins, const double* K, int V, int H,
+                         int W, int32_t* pixel, float* points, int32_t* counts, int32_t* status, gpn_stream_t stream);
+size_t gpn_view_fps_ws_bytes(int V);
+int gpn_view_fps(float* points, int64_t n_bound, const int32_t* counts, int32_t* status, int V, int m, int max_groups, int32_t* idx,
+                 void* ws, size_t ws_bytes, gpn_stream_t stream);
+int gpn_view_finish(const void* depth, int depth_bytes, const uint8_t* rgb, const int32_t* sem, const int32_t* ins, const float* npcs,
+                    const double* K, int V, int H, int W, const int32_t* pixel, const int32_t* idx, int m, int32_t* status,
+                    float* xyz, float* rgb_out, int32_t* sem_out, int32_t* ins_out, float* npcs_out, int32_t* pix_out, int32_t* gt,
+                    double* scale, gpn_stream_t stream);
+
+/* ================================================================================================
  * PF - pose fitting.  replaces the per-proposal numpy loop of gapartnet/misc/pose_fitting.py:4-147 (estimate_pose_from_npcs:
  * 5-point RANSAC over Umeyama similarity fits, Umeyama on the inliers, NPCS-aligned box; callers network/model.py:966-980,
  * structure/utils.py:172-188) for ALL proposals of a batch: two launches, float64 like the reference.
