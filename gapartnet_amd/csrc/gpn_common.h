@@ -202,6 +202,21 @@ bool spconv_msplit_supported(int K, int64_t n_dst, int cin, int cout);
 int spconv_msplit_launch(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
                          int cin, int cout, int accumulate, const ConvStats& stats, float* out, hipStream_t stream,
                          const DevRows& rows = DevRows());
+// the bf16 inference path (spconv_bf16.hip): argument check, conv launch, batched weight packing and the elementwise launches the
+// network executor's bf16 pass (net.hip, gpn_net_forward_bf16) is made of
+struct PackBf16Desc {
+  const float* W;
+  uint16_t* packed;
+  int K, cin, cout, oki;
+};
+int spconv_bf16_check(const char* who, int K, int64_t n_dst, int cin, int cout);
+int spconv_bf16_launch(const uint16_t* in, const uint16_t* packed, const int32_t* nbr, const int32_t* nbr_p, const int32_t* perm,
+                       int K, int64_t n_dst, int cin, int cout, const gpn_conv_epilogue_bf16_t* ep, void* out, hipStream_t stream);
+int pack_bf16_many(const PackBf16Desc* descs, int n, hipStream_t stream);
+int rows_to_bf16_launch(const float* x, int64_t total, uint16_t* y, hipStream_t stream);
+int bn_act_bf16_launch(const void* x, int x_is_f32, const uint16_t* res, const float* weight, const float* bias, const float* mean,
+                       const float* var, float eps, int64_t N, int C, int relu, int out_f32, void* y, hipStream_t stream);
+int concat_bf16_launch(const uint16_t* a, const uint16_t* b, uint16_t* dst, int64_t rows, int ca, int cb, hipStream_t stream);
 // weight-gradient contraction and its (batched) slice sums (spconv.hip); used by gpn_spconv_wgrad and the network executor
 constexpr int kWgradReduceJobs = 24;
 constexpr int kWgradSets = 4;

@@ -42,6 +42,8 @@ const char* kEntryPoints[] = {
     "gpn_proposals_voxel_mean_bwd", "gpn_proposals_revoxelize_ws_bytes", "gpn_proposals_revoxelize", "gpn_proposals_postprocess_ws_bytes", "gpn_proposals_postprocess", "gpn_proposals_postprocess_lds_proposals", "gpn_backbone_prepare_desc_words", "gpn_backbone_prepare_arena_bytes", "gpn_backbone_prepare", "gpn_scene_prepare_max_instances", "gpn_scene_prepare_ws_bytes", "gpn_scene_prepare", "gpn_pose_fit_ws_bytes", "gpn_pose_fit", "gpn_copy_many", "gpn_adam_blocks", "gpn_adam_step", "gpn_adam_step_gated", "gpn_prof_enable", "gpn_prof_bracket_overhead_us", "gpn_prof_reset", "gpn_prof_get", "gpn_prof_get_launches",
     "gpn_rulebook_subm3_dev", "gpn_rulebook_down_dev_ws_bytes", "gpn_rulebook_down_dev", "gpn_rulebook_down_lists_dev", "gpn_rulebook_identity_dev", "gpn_gather_rows_dev", "gpn_scatter_rows_csr_dev", "gpn_proposals_voxel_mean_dev", "gpn_proposals_targets_dev", "gpn_linear_fwd_dev", "gpn_linear_bwd_dev", "gpn_segmented_maxpool_fwd_dev", "gpn_segmented_maxpool_bwd_dev", "gpn_instance_iou_dev", "gpn_score_loss_dev", "gpn_npcs_loss_fwd_dev", "gpn_npcs_loss_bwd_dev",
     "gpn_view_max_instance_ids", "gpn_view_backproject", "gpn_view_fps_ws_bytes", "gpn_view_fps", "gpn_view_finish",
+    "gpn_spconv_pack_weights_bf16", "gpn_spconv_fwd_bf16", "gpn_rows_to_bf16", "gpn_bn_act_bf16", "gpn_net_forward_bf16_ws_bytes",
+    "gpn_net_forward_bf16",
     "gpn_last_error", "gpn_version"};
 }  // namespace
 

@@ -1031,3 +1031,193 @@ extern "C" int gpn_net_backward_pair(const gpn_net_op_t* ops, int n_ops, gpn_net
   return net_backward_impl(__func__, ops, n_ops, two, 2, n_slots, rbs, n_rbs, n_convs, n_bns, training, need_input_grad, ws,
                            ws_bytes, (hipStream_t)stream_);
 }
+
+// ---- the bf16 inference pass (include/gpn.h section C16; kernels in spconv_bf16.hip) -----------------------------------------------
+namespace {
+
+constexpr size_t kNoBuffer = ~(size_t)0;
+
+// What a bf16 pass holds in its workspace - the packed bf16 weights and ONE bf16 buffer per slot that is materialised - and which
+// BatchNorms ride in the conv before them.  A function of the tables alone: gpn_net_forward_bf16_ws_bytes and the pass share it.
+struct Bf16Plan {
+  std::vector<char> folded;        // BN op i is applied by CONV op i - 1 (whose own output slot is never materialised)
+  std::vector<size_t> slot_off;    // by slot: byte offset of its bf16 buffer, kNoBuffer = none
+  std::vector<size_t> packed_off;  // by CONV op: byte offset of its packed weight
+  int out_slot = -1;               // the slot that is written and never read: receives fp32
+  size_t total = 0;
+};
+
+int plan_bf16(const char* who, const gpn_net_op_t* ops, int n_ops, const gpn_net_slot_t* slots, int n_slots,
+              const gpn_net_rulebook_t* rbs, const gpn_net_conv_t* convs, Bf16Plan& plan) {
+  std::vector<int> readers(n_slots, 0), written(n_slots, 0);
+  bool slot0_bf16 = false;  // slot 0 has a reader other than a BatchNorm's input
+  for (int i = 0; i < n_ops; ++i) {
+    const gpn_net_op_t& op = ops[i];
+    if (op.src0 < 0 || op.src0 >= n_slots || op.dst < 0 || op.dst >= n_slots || op.src1 >= n_slots) {
+      gpn::set_error("%s: op %d: slot index out of range", who, i);
+      return GPN_ERR_ARG;
+    }
+    readers[op.src0]++;
+    if (op.src1 >= 0) readers[op.src1]++;
+    if ((op.src0 == 0 && op.kind != GPN_NET_BN) || op.src1 == 0) slot0_bf16 = true;
+  }
+  plan.folded.assign(n_ops, 0);
+  for (int i = 0; i + 1 < n_ops; ++i) {
+    const gpn_net_op_t &cv_op = ops[i], &bn_op = ops[i + 1];
+    if (cv_op.kind != GPN_NET_CONV || bn_op.kind != GPN_NET_BN || bn_op.src0 != cv_op.dst || readers[cv_op.dst] != 1) continue;
+    if (bn_op.src1 == cv_op.dst || bn_op.dst == cv_op.src0) continue;
+    plan.folded[i + 1] = 1;
+  }
+  for (int i = 0; i < n_ops; ++i)
+    if (!(ops[i].kind == GPN_NET_CONV && i + 1 < n_ops && plan.folded[i + 1])) written[ops[i].dst]++;
+  plan.out_slot = -1;
+  for (int s = 1; s < n_slots; ++s) {
+    if (written[s] > 1) {
+      gpn::set_error("%s: slot %d is written by more than one op", who, s);
+      return GPN_ERR_ARG;
+    }
+    if (written[s] && readers[s] == 0) {
+      if (plan.out_slot >= 0) {
+        gpn::set_error("%s: slots %d and %d are both written and never read: the program needs exactly one output slot", who,
+                       plan.out_slot, s);
+        return GPN_ERR_ARG;
+      }
+      plan.out_slot = s;
+    }
+  }
+  if (plan.out_slot < 0) {
+    gpn::set_error("%s: the program has no output slot (one that is written and never read)", who);
+    return GPN_ERR_ARG;
+  }
+  size_t off = 0;
+  plan.packed_off.assign(n_ops, kNoBuffer);
+  for (int i = 0; i < n_ops; ++i) {
+    if (ops[i].kind != GPN_NET_CONV) continue;
+    const gpn_net_conv_t& cv = convs[ops[i].param];
+    plan.packed_off[i] = off;
+    off += gpn::align_up((size_t)rbs[ops[i].rulebook].K * cv.cin * cv.cout * sizeof(uint16_t));
+  }
+  plan.slot_off.assign(n_slots, kNoBuffer);
+  for (int s = 0; s < n_slots; ++s) {
+    if (s == 0 ? !slot0_bf16 : (!written[s] || s == plan.out_slot)) continue;
+    plan.slot_off[s] = off;
+    off += gpn::align_up((size_t)slots[s].rows * slots[s].channels * sizeof(uint16_t));
+  }
+  plan.total = off;
+  return GPN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gpn_net_forward_bf16_ws_bytes(const gpn_net_op_t* ops, int n_ops, const gpn_net_slot_t* slots, int n_slots,
+                                                const gpn_net_rulebook_t* rulebooks, const gpn_net_conv_t* convs) {
+  if (!ops || !slots || n_ops < 1 || n_slots < 1) return 0;
+  Bf16Plan plan;
+  if (plan_bf16(__func__, ops, n_ops, slots, n_slots, rulebooks, convs, plan) != GPN_OK) return 0;
+  return plan.total;
+}
+
+extern "C" int gpn_net_forward_bf16(const gpn_net_op_t* ops, int n_ops, gpn_net_slot_t* slots, int n_slots,
+                                    const gpn_net_rulebook_t* rbs, int n_rbs, const gpn_net_conv_t* convs, int n_convs,
+                                    const gpn_net_bn_t* bns, int n_bns, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
+  const char* who = __func__;
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc = check_program(who, ops, n_ops, slots, n_slots, rbs, n_rbs, convs, n_convs, bns, n_bns);
+  if (rc) return rc;
+  // ---- everything is validated before the first launch ----
+  for (int s = 0; s < n_slots; ++s)
+    if (slots[s].rows_dev) {
+      gpn::set_error("%s: slot %d: device-counted row counts (rows_dev) are not supported by the bf16 pass", who, s);
+      return GPN_ERR_ARG;
+    }
+  for (int i = 0; i < n_ops; ++i) {
+    const gpn_net_op_t& op = ops[i];
+    if (op.kind == GPN_NET_CONV) {
+      const gpn_net_rulebook_t& rb = rbs[op.rulebook];
+      const gpn_net_conv_t& cv = convs[op.param];
+      rc = gpn::spconv_bf16_check(who, rb.K, rb.n_dst, cv.cin, cv.cout);
+      if (rc) return rc;
+      if ((rb.nbr_p == nullptr) != (rb.perm == nullptr)) {
+        gpn::set_error("%s: op %d: a tile order needs both nbr_p and perm", who, i);
+        return GPN_ERR_ARG;
+      }
+    } else if (op.kind == GPN_NET_BN) {
+      const gpn_net_bn_t& bn = bns[op.param];
+      if (!bn.weight || !bn.bias || !bn.running_mean || !bn.running_var) {
+        gpn::set_error("%s: op %d: BatchNorm needs weight, bias, running_mean and running_var (null pointer)", who, i);
+        return GPN_ERR_ARG;
+      }
+    }
+  }
+  if (n_ops < 1) {
+    gpn::set_error("%s: empty program", who);
+    return GPN_ERR_ARG;
+  }
+  Bf16Plan plan;
+  rc = plan_bf16(who, ops, n_ops, slots, n_slots, rbs, convs, plan);
+  if (rc) return rc;
+  for (int i = 0; i < n_ops; ++i)
+    if (ops[i].kind == GPN_NET_CONCAT && ops[i].dst == plan.out_slot) {
+      gpn::set_error("%s: op %d: a concat cannot write the (fp32) output slot", who, i);
+      return GPN_ERR_ARG;
+    }
+  if (!slots[0].data || !slots[plan.out_slot].data) {
+    gpn::set_error("%s: null activation pointer (input slot 0 / output slot %d)", who, plan.out_slot);
+    return GPN_ERR_ARG;
+  }
+  if (!ws || ws_bytes < plan.total) {
+    gpn::set_error("%s: workspace too small (%zu needed, %zu given)", who, plan.total, ws_bytes);
+    return GPN_ERR_WS;
+  }
+  // ---- launches ----
+  char* base = static_cast<char*>(ws);
+  auto buf = [&](int s) { return reinterpret_cast<uint16_t*>(base + plan.slot_off[s]); };
+  std::vector<gpn::PackBf16Desc> descs;
+  for (int i = 0; i < n_ops; ++i)
+    if (ops[i].kind == GPN_NET_CONV) {
+      const gpn_net_conv_t& cv = convs[ops[i].param];
+      descs.push_back(gpn::PackBf16Desc{cv.W, reinterpret_cast<uint16_t*>(base + plan.packed_off[i]), rbs[ops[i].rulebook].K, cv.cin,
+                                        cv.cout, 1});
+    }
+  rc = gpn::pack_bf16_many(descs.data(), (int)descs.size(), stream);
+  if (rc) return rc;
+  if (plan.slot_off[0] != kNoBuffer) {
+    rc = gpn::rows_to_bf16_launch(slots[0].data, slots[0].rows * slots[0].channels, buf(0), stream);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < n_ops; ++i) {
+    const gpn_net_op_t& op = ops[i];
+    if (plan.folded[i]) continue;  // (applied by the conv before it)
+    const gpn_net_slot_t &s0 = slots[op.src0], &d = slots[op.dst];
+    if (op.kind == GPN_NET_CONV) {
+      const gpn_net_rulebook_t& rb = rbs[op.rulebook];
+      const gpn_net_conv_t& cv = convs[op.param];
+      gpn_conv_epilogue_bf16_t ep{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, 0};
+      int dst = op.dst;
+      if (i + 1 < n_ops && plan.folded[i + 1]) {
+        const gpn_net_op_t& bo = ops[i + 1];
+        const gpn_net_bn_t& bn = bns[bo.param];
+        ep.mean = bn.running_mean, ep.var = bn.running_var, ep.weight = bn.weight, ep.bias = bn.bias;
+        ep.res = bo.src1 >= 0 ? buf(bo.src1) : nullptr;
+        ep.eps = bn.eps, ep.relu = (bo.flags & GPN_NET_RELU) ? 1 : 0;
+        dst = bo.dst;
+      }
+      ep.out_f32 = dst == plan.out_slot ? 1 : 0;
+      void* out = ep.out_f32 ? static_cast<void*>(slots[dst].data) : static_cast<void*>(buf(dst));
+      rc = gpn::spconv_bf16_launch(buf(op.src0), reinterpret_cast<const uint16_t*>(base + plan.packed_off[i]), rb.nbr, rb.nbr_p,
+                                   rb.perm, rb.K, rb.n_dst, cv.cin, cv.cout, &ep, out, stream);
+    } else if (op.kind == GPN_NET_BN) {
+      const gpn_net_bn_t& bn = bns[op.param];
+      const bool from_input = op.src0 == 0;  // the fp32 input itself
+      const int out_f32 = op.dst == plan.out_slot ? 1 : 0;
+      rc = gpn::bn_act_bf16_launch(from_input ? static_cast<const void*>(s0.data) : static_cast<const void*>(buf(op.src0)),
+                                   from_input ? 1 : 0, op.src1 >= 0 ? buf(op.src1) : nullptr, bn.weight, bn.bias, bn.running_mean,
+                                   bn.running_var, bn.eps, s0.rows, bn.C, (op.flags & GPN_NET_RELU) ? 1 : 0, out_f32,
+                                   out_f32 ? static_cast<void*>(d.data) : static_cast<void*>(buf(op.dst)), stream);
+    } else {
+      rc = gpn::concat_bf16_launch(buf(op.src0), buf(op.src1), buf(op.dst), d.rows, s0.channels, slots[op.src1].channels, stream);
+    }
+    if (rc) return rc;
+  }
+  return GPN_OK;
+}

@@ -1393,3 +1393,99 @@ def view_convert(depth, rgb, sem, ins, npcs, K, m, max_groups=0):
                                    ptr(f["sem"]), ptr(f["ins"]), ptr(f["npcs"]), ptr(f["pix"]), ptr(f["gt"]), ptr(f["scale"]),
                                    _stream()), "gpn_view_finish")
     return buf, layout
+
+
+# ---------------------------------------------------------------------------------------------------- C16
+# The opt-in bf16 INFERENCE ops (include/gpn.h section C16, csrc/spconv_bf16.hip): torch.bfloat16 tensors in and out, fp32
+# accumulation, one round-to-nearest-even per stored activation.  No autograd: an input that requires grad is an error.
+class _EpilogueBf16(_C.ctypes.Structure):
+    _fields_ = [("mean", _C.ctypes.c_void_p), ("var", _C.ctypes.c_void_p), ("weight", _C.ctypes.c_void_p),
+                ("bias", _C.ctypes.c_void_p), ("res", _C.ctypes.c_void_p), ("eps", _C.ctypes.c_float),
+                ("relu", _C.ctypes.c_int32), ("out_f32", _C.ctypes.c_int32)]
+
+
+def _inference_only(*tensors):
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            raise _C.GpnError("the bf16 ops are inference-only (no autograd): an input requires grad")
+
+
+def _as_bf16(t, what):
+    if t.dtype != torch.bfloat16:
+        raise _C.GpnError(f"{what} must be a torch.bfloat16 tensor, got {t.dtype}")
+    return t.contiguous()
+
+
+def conv_pack_bf16(W, layout="kio"):
+    """fp32 weight, canonical [K, Cin, Cout] ("kio") or parameter layout [Cout, K, Cin] ("oki"), -> the bf16 kernel's packed
+    weight (flat bfloat16 tensor of K * Cin * Cout elements, each rounded to nearest even)"""
+    dev = _dev(W)
+    _inference_only(W)
+    W = _c(W, torch.float32)
+    K, cin, cout = _wdims(W, layout)
+    packed = torch.empty((K * cin * cout,), dtype=torch.bfloat16, device=dev)
+    check(_C.lib().gpn_spconv_pack_weights_bf16(ptr(W), i32(K), i32(cin), i32(cout), i32(LAYOUT_OKI if layout == "oki" else 0),
+                                                ptr(packed), _stream()), "gpn_spconv_pack_weights_bf16")
+    return packed
+
+
+def conv_fwd_bf16(features, packed, rb: Rulebook, cin, cout, bn=None, res=None, relu=False, out_f32=False, out=None):
+    """conv over ``rb`` (its tile order when it has one) on bf16 ``features`` [n_src, cin] and a ``conv_pack_bf16`` weight, with
+    the fused epilogue: ``bn`` = (running_mean, running_var, weight, bias, eps) fp32 or None, ``res`` a bf16 [n_dst, cout]
+    residual or None, ``relu``.  -> [n_dst, cout] bfloat16, or float32 (unrounded) with ``out_f32``.  ``out``: write there."""
+    dev = _dev(features, packed)
+    _inference_only(features, packed, res, *(bn[:4] if bn is not None else ()))
+    features = _as_bf16(features, "features")
+    packed = _as_bf16(packed, "packed weight")
+    assert features.shape == (rb.n_src, cin), (features.shape, rb.n_src, cin)
+    assert packed.numel() == rb.K * cin * cout, (packed.numel(), rb.K, cin, cout)
+    ep = _EpilogueBf16(0, 0, 0, 0, 0, 0.0, 1 if relu else 0, 1 if out_f32 else 0)
+    keep = []
+    if bn is not None:
+        mean, var, weight, bias, eps = bn
+        keep = [_c(t, torch.float32) for t in (mean, var, weight, bias)]
+        assert all(t.numel() == cout for t in keep)
+        ep.mean, ep.var, ep.weight, ep.bias = (t.data_ptr() for t in keep)
+        ep.eps = float(eps)
+    if res is not None:
+        res = _as_bf16(res, "residual")
+        assert res.shape == (rb.n_dst, cout), (res.shape, rb.n_dst, cout)
+        ep.res = res.data_ptr()
+    if out is None:
+        out = torch.empty((rb.n_dst, cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dev)
+    check(_C.lib().gpn_spconv_fwd_bf16(ptr(features), ptr(packed), ptr(rb.nbr), ptr(rb.nbr_p), ptr(rb.perm), i32(rb.K),
+                                       i64(rb.n_dst), i32(cin), i32(cout), _C.ctypes.byref(ep), ptr(out), _stream()),
+          "gpn_spconv_fwd_bf16")
+    return out
+
+
+def rows_to_bf16(x):
+    """fp32 [n, C] -> bfloat16, round to nearest even"""
+    dev = _dev(x)
+    _inference_only(x)
+    x = _c(x, torch.float32)
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
+    check(_C.lib().gpn_rows_to_bf16(ptr(x), i64(x.shape[0]), i32(x.numel() // max(x.shape[0], 1)), ptr(y), _stream()),
+          "gpn_rows_to_bf16")
+    return y
+
+
+def bn_act_bf16(x, weight, bias, running_mean, running_var, eps, relu, res=None):
+    """eval-mode BatchNorm [+ bf16 residual] [+ ReLU] on a float32 or bfloat16 [N, C] tensor -> bfloat16 (the bf16 conv's
+    epilogue arithmetic on a tensor no conv produced)"""
+    dev = _dev(x)
+    _inference_only(x, weight, bias, res)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise _C.GpnError(f"bn_act_bf16 takes float32 or bfloat16 rows, got {x.dtype}")
+    x = x.contiguous()
+    N, C = x.shape
+    pars = [_c(t, torch.float32) for t in (weight, bias, running_mean, running_var)]
+    assert all(t.numel() == C for t in pars)
+    if res is not None:
+        res = _as_bf16(res, "residual")
+        assert res.shape == x.shape
+    y = torch.empty((N, C), dtype=torch.bfloat16, device=dev)
+    check(_C.lib().gpn_bn_act_bf16(ptr(x), i32(1 if x.dtype == torch.float32 else 0), ptr(res), ptr(pars[0]), ptr(pars[1]),
+                                   ptr(pars[2]), ptr(pars[3]), f32(eps), i64(N), i32(C), i32(1 if relu else 0), ptr(y), _stream()),
+          "gpn_bn_act_bf16")
+    return y

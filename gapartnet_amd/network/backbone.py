@@ -90,6 +90,11 @@ class SparseUNet(nn.Module):
     # run forward / backward of the whole network through the native layer-program executor (network/net_exec.py,
     # csrc/net.hip) instead of module by module; same kernels, same results, one library call per direction
     use_native_executor = True
+    # None (default): every pass in fp32.  torch.bfloat16: INFERENCE passes - eval mode with gradients disabled - of the native
+    # executor run in bf16 (gpn_net_forward_bf16: bf16 activations and weights, fp32 accumulation, fp32 output); training passes,
+    # eval passes with gradients enabled and inputs with device-counted rows keep the fp32 path bit for bit.  Any other value
+    # raises ValueError at the first forward.
+    inference_dtype = None
 
     def __init__(self, stem: Optional[nn.Module], ublock: UBlock):
         super().__init__()
@@ -97,6 +102,8 @@ class SparseUNet(nn.Module):
         self.ublock = ublock
 
     def forward(self, x: spconv.SparseConvTensor) -> spconv.SparseConvTensor:
+        if self.inference_dtype is not None and self.inference_dtype is not torch.bfloat16:
+            raise ValueError(f"SparseUNet.inference_dtype must be None or torch.bfloat16, got {self.inference_dtype!r}")
         if self.use_native_executor and backend.raw().name == "hip":
             from . import net_exec
             out = net_exec.run(self, x)

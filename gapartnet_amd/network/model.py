@@ -84,6 +84,10 @@ class GAPartNet(LightningModule):
         ckpt: str = "",
         # not in the reference: voxel size used when scenes reach the model un-voxelised (on-device voxelisation)
         voxel_size: Sequence[float] = (0.01, 0.01, 0.01),
+        # not in the reference: torch.bfloat16 = the backbone's inference passes (eval mode, gradients disabled) run in bf16
+        # (SparseUNet.inference_dtype); None = fp32 everywhere.  The ScoreNet / NPCS-Net U-Nets (paired passes, device-counted
+        # rows) stay fp32 either way.
+        inference_dtype: Optional[torch.dtype] = None,
     ):
         super().__init__()
         self.save_hyperparameters()
@@ -138,6 +142,7 @@ class GAPartNet(LightningModule):
         block_repeat = self.backbone_cfg["block_repeat"]
         width = channels[0]
         self.backbone = SparseUNet.build(in_channels, channels, block_repeat, norm_fn)
+        self.inference_dtype = inference_dtype
         self.sem_seg_head = nn.Linear(width, self.num_part_classes)
         self.offset_head = nn.Sequential(nn.Linear(width, width), norm_fn(width), nn.ReLU(inplace=True),
                                          nn.Linear(width, 3))
@@ -157,6 +162,16 @@ class GAPartNet(LightningModule):
                 print("missing_keys:", missing_keys)
             if len(unexpected_keys) > 0:
                 print("unexpected_keys:", unexpected_keys)
+
+    @property
+    def inference_dtype(self):
+        """None (fp32) or torch.bfloat16: the number format of the BACKBONE's inference passes (SparseUNet.inference_dtype).  The
+        ScoreNet / NPCS-Net U-Nets stay fp32."""
+        return self.backbone.inference_dtype
+
+    @inference_dtype.setter
+    def inference_dtype(self, value):
+        self.backbone.inference_dtype = value
 
     # ------------------------------------------------------------------------------------------ forward pieces
     def forward_backbone(self, pc_batch: PointCloudBatch) -> torch.Tensor:

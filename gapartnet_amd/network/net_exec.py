@@ -760,6 +760,37 @@ class _NetFnAutograd(torch.autograd.Function):
         return (din, None, None, None) + grads
 
 
+def _forward_bf16(features, prog: NetProgram, rows, rb_table, rb_objs):
+    """one INFERENCE pass through gpn_net_forward_bf16 (include/gpn.h section C16): fp32 features in, fp32 output; the interior
+    activations and the packed weights live in the shared scratch buffer as bf16.  No autograd."""
+    from ..hip_ops import _fast_ws
+    features = features.contiguous()
+    dev = features.device
+    slot_rows = rows[prog.slot_level_np]
+    slots = np.zeros(len(prog.slot_level), SLOT_DT)
+    slots["rows"] = slot_rows
+    slots["channels"] = prog.slot_channels_np
+    o = prog.out_slot
+    out = torch.empty((int(slot_rows[o]), int(prog.slot_channels_np[o])), dtype=torch.float32, device=dev)
+    slots["data"][0] = features.data_ptr()
+    slots["data"][o] = out.data_ptr()
+    conv_table, bn_table = prog.static_tables(prog.params())
+    L = _C.lib()
+    fn = L.gpn_net_forward_bf16
+    tables = (_vp(prog.ops_np), len(prog.ops_np), _vp(slots), len(slots), _vp(rb_table))
+    args = tables + (len(rb_table), _vp(conv_table), len(conv_table), _vp(bn_table), len(bn_table))
+    ws_ptr, ws_size, stream = _fast_ws(dev)
+    rc = fn(*args, ctypes.c_void_p(ws_ptr), ctypes.c_size_t(ws_size), ctypes.c_void_p(stream))
+    if rc == 2:  # workspace too small: size it from the library's own figure and retry
+        need = L.gpn_net_forward_bf16_ws_bytes(*tables, _vp(conv_table))
+        ws_ptr, ws_size, stream = _fast_ws(dev, int(need))
+        rc = fn(*args, ctypes.c_void_p(ws_ptr), ctypes.c_size_t(ws_size), ctypes.c_void_p(stream))
+    if rc:
+        raise _C.GpnError(f"gpn_net_forward_bf16 failed: {L.gpn_last_error().decode('utf-8', 'replace')}")
+    _log_forward(prog, rb_objs)
+    return out
+
+
 def program_for(unet) -> Optional[NetProgram]:
     """the cached program of a SparseUNet (rebuilt if its module tree changed); None if it cannot be expressed"""
     cached = unet.__dict__.get("_net_program")
@@ -833,6 +864,11 @@ def run(unet, x):
         rows, rb_table, rb_objs, levels = prog.rulebooks(x)
     if int(rows.min()) < 1 or x.features.shape[1] != prog.slot_channels[0]:
         return None
+    if unet.inference_dtype is torch.bfloat16 and not training and not torch.is_grad_enabled() and lvl_dev is None:
+        # the opt-in reduced-precision inference pass: exactly the condition under which the fp32 pass runs as GPN_NET_INFERENCE
+        out = _forward_bf16(x.features, prog, rows, rb_table, rb_objs)
+        lvl = prog.slot_level[prog.out_slot]
+        return _out_tensor(out, levels[lvl][0], levels[lvl][1], x, None)
     if training:
         with torch.no_grad():
             _count_batches(prog.buffers("num_batches_tracked"), x)

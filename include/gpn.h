@@ -377,6 +377,58 @@ int gpn_net_backward_pair(const gpn_net_op_t* ops, int n_ops, gpn_net_slot_t* sl
                           int n_bns, int training, int need_input_grad, void* ws, size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * C16 - opt-in reduced-precision INFERENCE path (csrc/spconv_bf16.hip): forward only, off by default, separate entry points;
+ * nothing of the fp32 path runs through it.  bf16 tensors are passed as uint16_t (the upper half of the fp32 bit pattern).
+ * Numerics contract: operands (activations, weights) are bf16; a product of two bf16 values is exact in fp32; sums are fp32
+ * (v_mfma_f32_16x16x32_bf16, and v_mfma_f32_16x16x16_bf16 for the odd 16-channel block of the widths 16, 48, 80, 112), in a
+ * fixed order - the 32-channel blocks of all taps one chain (ascending tap, within a tap ascending block), the odd 16-channel
+ * block of all taps a second chain, result = chain32 + chain16 - that does not depend on the tile order or on the kernel
+ * instantiation; taps a row does not have contribute exact zeros; launches are deterministic.  The epilogue runs in fp32 and a
+ * stored activation is rounded ONCE, to nearest even; the network's output is fp32, unrounded.
+ *   gpn_spconv_pack_weights_bf16: fp32 weight, canonical [K][Cin][Cout] (flags = 0) or parameter layout [Cout][K][Cin]
+ *     (flags = GPN_LAYOUT_OKI; no other flag), -> K*cin*cout bf16 in the kernel's fragment order, each rounded to nearest even.
+ *   gpn_spconv_fwd_bf16: in [n_src, cin] bf16, the tables of gpn_spconv_fwd_ordered (nbr [K][n_dst], -1 = none; nbr_p / perm the
+ *     optional tile order, both or neither), 1 <= K <= 27, cin / 16 in {1..8, 10, 12, 14}, cout % 16 == 0,
+ *     8 n_dst * 2 max(cin, cout) < 2^31 (32-bit byte offsets; GPN_ERR_ARG beyond).  Epilogue per output element, in fp32:
+ *       v = (acc - mean) * (1 / sqrtf(var + eps)) * weight + bias     (mean != NULL; var, weight, bias then required)
+ *       v += res[e]                                                   (res != NULL: bf16 [n_dst, cout], widened exactly)
+ *       v = max(0, v)                                                 (relu)
+ *     then out [n_dst, cout] = v rounded to bf16 (out_f32 == 0) or v itself as fp32 (out_f32 != 0).  ep == NULL: no epilogue,
+ *     bf16 out.  Every output row is written once by one wave: no workspace.
+ *   gpn_rows_to_bf16: y = x rounded to nearest even, [n, C].
+ *   gpn_bn_act_bf16: y = act(bn_eval(x) [+ res]) with the epilogue's arithmetic on a tensor no conv produced; x fp32
+ *     (x_is_f32 != 0) or bf16, y bf16.
+ *   gpn_net_forward_bf16: the op program of section U over the same tables as gpn_net_forward in GPN_NET_INFERENCE mode (running
+ *     statistics; a BatchNorm that directly and solely follows a conv is applied in that conv's epilogue).  slots[0].data is the
+ *     fp32 input; the output slot (the one slot that is written and never read) receives fp32, unrounded; every other slot's
+ *     data / grad is ignored and may be NULL: interior activations live in the workspace as bf16, one buffer per slot that is
+ *     materialised.  A BatchNorm that reads slot 0 reads the fp32 input; every other reader of slot 0 reads its bf16 rounding.
+ *     Weights are packed to bf16 into the workspace on every call.  Before the first launch the program is validated as by
+ *     gpn_net_forward, and: no slot may carry rows_dev, conv widths must be supported by gpn_spconv_fwd_bf16, every BatchNorm
+ *     needs weight, bias, running_mean and running_var, the workspace must hold gpn_net_forward_bf16_ws_bytes. */
+typedef struct gpn_conv_epilogue_bf16 {
+  const float* mean;
+  const float* var;
+  const float* weight;
+  const float* bias;
+  const uint16_t* res;
+  float eps;
+  int32_t relu;
+  int32_t out_f32;
+} gpn_conv_epilogue_bf16_t;
+int gpn_spconv_pack_weights_bf16(const float* W, int K, int cin_w, int cout_w, int flags, uint16_t* packed, gpn_stream_t stream);
+int gpn_spconv_fwd_bf16(const uint16_t* in, const uint16_t* packed_w, const int32_t* nbr, const int32_t* nbr_p, const int32_t* perm,
+                        int K, int64_t n_dst, int cin, int cout, const gpn_conv_epilogue_bf16_t* ep, void* out, gpn_stream_t stream);
+int gpn_rows_to_bf16(const float* x, int64_t n, int C, uint16_t* y, gpn_stream_t stream);
+int gpn_bn_act_bf16(const void* x, int x_is_f32, const uint16_t* res, const float* weight, const float* bias, const float* mean,
+                    const float* var, float eps, int64_t N, int C, int relu, uint16_t* y, gpn_stream_t stream);
+size_t gpn_net_forward_bf16_ws_bytes(const gpn_net_op_t* ops, int n_ops, const gpn_net_slot_t* slots, int n_slots,
+                                     const gpn_net_rulebook_t* rulebooks, const gpn_net_conv_t* convs);
+int gpn_net_forward_bf16(const gpn_net_op_t* ops, int n_ops, gpn_net_slot_t* slots, int n_slots,
+                         const gpn_net_rulebook_t* rulebooks, int n_rulebooks, const gpn_net_conv_t* convs, int n_convs,
+                         const gpn_net_bn_t* bns, int n_bns, void* ws, size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * B — ball query.  replaces epic_ops.ball_query.ball_query (network/grouping_utils.py:119-128).
  * points [Np,3], query [Q,3], batch_indices [Q] i32, batch_offsets [S+1] i32 (CSR over points),
  * point_labels [Np] / query_labels [Q] i32 (both may be NULL = no label filter).

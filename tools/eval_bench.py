@@ -31,6 +31,11 @@ def main():
     ap.add_argument("--ab-bn-fusion", action="store_true",
                     help="alternate epochs with the BatchNorm in the conv epilogues (inference passes, round 6) and as launches of its "
                          "own; reports the median step time of each")
+    ap.add_argument("--inference-dtype", choices=["fp32", "bf16"], default="fp32",
+                    help="bf16: the backbone's inference passes in bf16 (GAPartNet.inference_dtype = torch.bfloat16)")
+    ap.add_argument("--ab-inference-dtype", action="store_true",
+                    help="alternate epochs with the backbone's inference passes in bf16 and in fp32; reports the median step time and "
+                         "the logged mAP of each")
     args = ap.parse_args()
     import importlib.util
     spec = importlib.util.spec_from_file_location("gpn_bench", os.path.join(ROOT, "bench.py"))
@@ -44,6 +49,8 @@ def main():
     model = make_model((0, 0)).eval()
     model.load_state_dict(recipe.name_keyed_state(model))
     model = model.to(dev)
+    if args.inference_dtype == "bf16":
+        model.inference_dtype = torch.bfloat16
     logged = {}
     model._log_sink = lambda name, value, bs, sync: logged.__setitem__(name, value)
     model.defer_validation_outputs = True  # (what gapartnet_amd.trainer.Trainer's evaluation loop sets)
@@ -51,11 +58,15 @@ def main():
              for l in range(3)]
     step_ms, end_ms, kept = [], [], 0
     by_mode = {0: [], 1: []}
+    map_by_mode = {0: [], 1: []}
+    ab = args.ab_bn_fusion or args.ab_inference_dtype
     from gapartnet_amd import _C
     with torch.no_grad():
-        for epoch in range((2 * args.epochs if args.ab_bn_fusion else args.epochs) + 1):  # epoch 0 warms up
+        for epoch in range((2 * args.epochs if ab else args.epochs) + (2 if args.ab_inference_dtype else 1)):  # epoch 0 (0, 1) warms up
             if args.ab_bn_fusion:
                 _C.lib().gpn_net_bn_fusion(epoch % 2)
+            if args.ab_inference_dtype:
+                model.inference_dtype = torch.bfloat16 if epoch % 2 else None
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for l in range(3):
@@ -71,12 +82,20 @@ def main():
             model.on_validation_epoch_end()
             torch.cuda.synchronize()
             t2 = time.perf_counter()
-            if epoch > 0:
+            if epoch > (1 if args.ab_inference_dtype else 0):
                 step_ms.append((t1 - t0) / (3 * args.steps) * 1e3)
                 end_ms.append((t2 - t1) * 1e3)
                 by_mode[epoch % 2].append(step_ms[-1])
+                map_by_mode[epoch % 2].append(float(logged.get("val/mAP", float("nan"))))
     step_ms.sort(); end_ms.sort()
     ms = step_ms[len(step_ms) // 2]
+    if args.ab_inference_dtype:
+        med = lambda v: sorted(v)[len(v) // 2]
+        print(json.dumps({"ms_per_validation_step": {"bf16": med(by_mode[1]), "fp32": med(by_mode[0])},
+                          "mAP_logged": {"bf16": map_by_mode[1][-1], "fp32": map_by_mode[0][-1]},
+                          "epochs_each": args.epochs, "all": {"bf16": by_mode[1], "fp32": by_mode[0]}, "batch": args.batch,
+                          "points": args.points}))
+        return
     if args.ab_bn_fusion:
         _C.lib().gpn_net_bn_fusion(1)
         med = lambda v: sorted(v)[len(v) // 2]
@@ -87,6 +106,7 @@ def main():
                       "ms_per_validation_step": ms, "epoch_end_ms": end_ms[len(end_ms) // 2],
                       "steps_per_epoch": 3 * args.steps, "batch": args.batch, "points": args.points,
                       "proposals_kept_last_step": kept, "mAP_logged": float(logged.get("val/mAP", float("nan"))),
+                      "inference_dtype": args.inference_dtype,
                       "config": "BASELINE config 2 shape (full pipeline eval, bs 4 x 20k), seeded weights (release.ckpt absent)"}))
 
 
