@@ -1395,6 +1395,107 @@ def view_convert(depth, rgb, sem, ins, npcs, K, m, max_groups=0):
     return buf, layout
 
 
+# ---------------------------------------------------------------------------------------------------- VS (test-time rendering)
+VISU_RGB, VISU_LABEL, VISU_LABEL_MOD20, VISU_LABEL_MOD19P1, VISU_BLANK = 0, 1, 2, 3, 4
+VISU_MAX_LAYERS = 16
+
+
+class _VisuLayer(_C.ctypes.Structure):
+    _fields_ = [("kind", _C.ctypes.c_int32), ("row", _C.ctypes.c_int32), ("col", _C.ctypes.c_int32),
+                ("offset", _C.ctypes.c_float), ("src", _C.ctypes.c_void_p)]
+
+
+def scene_maps(valid_indices, sorted_indices, proposal_offsets, npcs_valid_mask, npcs_preds, n_rows):
+    """one batch's kept proposals -> (ins_map [N] i32, npcs_map [N,3] f32, fit_npcs [M,3] f32) (include/gpn.h section VS);
+    any of the proposal tensors may be empty"""
+    dev = _dev(valid_indices, sorted_indices, proposal_offsets, npcs_valid_mask, npcs_preds)
+    vi, si, po = _c(valid_indices, torch.int64), _c(sorted_indices, torch.int64), _c(proposal_offsets, torch.int64)
+    mask, preds = _c(npcs_valid_mask, torch.uint8), _c(npcs_preds, torch.float32)
+    N, M, P = int(n_rows), int(si.shape[0]), max(int(po.shape[0]) - 1, 0)
+    if mask.shape[0] != M or preds.dim() != 2 or preds.shape[1] != 3:
+        raise _C.GpnError("scene_maps: npcs_valid_mask must be [M] and npcs_preds [Mv,3]")
+    ins_map = torch.empty((N,), dtype=torch.int32, device=dev)
+    npcs_map = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    fit_npcs = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_scene_maps_ws_bytes(i64(N), i64(M)), dev)
+    check(L.gpn_scene_maps(ptr(vi), i64(vi.shape[0]), ptr(si), ptr(po), i64(P), ptr(mask), i64(M), ptr(preds),
+                           i64(preds.shape[0]), i64(N), ptr(ins_map), ptr(npcs_map), ptr(fit_npcs), ptr(ws), szt(ws.numel()),
+                           _stream()), "gpn_scene_maps")
+    return ins_map, npcs_map, fit_npcs
+
+
+def _cam(fx, fy, u0, v0):
+    d = _C.ctypes.c_double
+    return d(float(fx)), d(float(fy)), d(float(u0)), d(float(v0))
+
+
+def points_winner(xyz, scene_offsets, trans, H, W, fx, fy, u0, v0):
+    """xyz [n,3] f32 (normalised frame, scenes as the CSR scene_offsets [S+1]), trans [S,4] f64 = (r, cx, cy, cz)
+    -> winner [S,H,W] i32: the highest point index of the scene covering each pixel, -1 where none"""
+    dev = _dev(xyz, scene_offsets, trans)
+    xyz, off, trans = _c(xyz, torch.float32), _c(scene_offsets, torch.int64), _c(trans, torch.float64)
+    S = int(off.shape[0]) - 1
+    if S < 0 or trans.numel() != S * 4 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _C.GpnError("points_winner: xyz must be [n,3], scene_offsets [S+1] and trans [S,4]")
+    winner = torch.empty((S, int(H), int(W)), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_points_winner(ptr(xyz), ptr(off), i64(xyz.shape[0]), ptr(trans), i32(S), i32(H), i32(W),
+                                     *_cam(fx, fy, u0, v0), ptr(winner), _stream()), "gpn_points_winner")
+    return winner
+
+
+def points_paint(winner, scene_offsets, layers, palette, canvas, edge):
+    """paints every layer of every scene into canvas [S,CH,CW,3] u8 in one launch.  layers: (kind, source, tile row, tile col[,
+    offset]) with source a per-point tensor over all scenes' rows ([n,3] f32 for VISU_RGB, [n] i32 for the label kinds, None for
+    VISU_BLANK); palette [K,3] u8"""
+    dev = _dev(winner, scene_offsets, palette, canvas)
+    S, H, W = winner.shape
+    off = _c(scene_offsets, torch.int64)
+    if canvas.dtype != torch.uint8 or not canvas.is_contiguous() or canvas.dim() != 4 or canvas.shape[0] != S or canvas.shape[3] != 3:
+        raise _C.GpnError("points_paint: canvas must be a contiguous [S,CH,CW,3] uint8 tensor")
+    if winner.dtype != torch.int32 or not winner.is_contiguous():
+        raise _C.GpnError("points_paint: winner must be a contiguous int32 tensor")
+    if len(layers) > VISU_MAX_LAYERS:
+        raise _C.GpnError(f"points_paint: at most {VISU_MAX_LAYERS} layers per call")
+    arr = (_VisuLayer * max(len(layers), 1))()
+    keep = []
+    for k, layer in enumerate(layers):
+        kind, src, row, col = layer[:4]
+        offset = float(layer[4]) if len(layer) > 4 else 0.0
+        if kind != VISU_BLANK:
+            _dev(src)
+            src = _c(src, torch.float32 if kind == VISU_RGB else torch.int32)
+            if (src.dim() != 2 or src.shape[1] != 3) if kind == VISU_RGB else src.dim() != 1:
+                raise _C.GpnError("points_paint: a VISU_RGB source must be [n,3], a label source [n]")
+            keep.append(src)
+        arr[k] = _VisuLayer(int(kind), int(row), int(col), offset, src.data_ptr() if kind != VISU_BLANK else None)
+    palette = _c(palette, torch.uint8)
+    check(_C.lib().gpn_points_paint(ptr(winner), ptr(off), i32(S), i32(H), i32(W), arr, i32(len(layers)), ptr(palette),
+                                    i32(palette.shape[0]), i32(edge), i32(canvas.shape[1]), i32(canvas.shape[2]), ptr(canvas),
+                                    _stream()), "gpn_points_paint")
+    return canvas
+
+
+def boxes_draw(bbox, box_scene, trans, H, W, fx, fy, u0, v0, tiles, canvas, edge):
+    """draws every box (bbox [Q,8,3] f64, normalised frame; box_scene [Q]) into the listed tiles [(row, col), ...] of its scene's
+    panel in canvas [S,CH,CW,3] u8, box by box in the reference's draw order (include/gpn.h section VS: the line rule)"""
+    dev = _dev(bbox, box_scene, trans, canvas)
+    bbox, box_scene, trans = _c(bbox, torch.float64), _c(box_scene, torch.int32), _c(trans, torch.float64)
+    Q, S = int(bbox.shape[0]), int(canvas.shape[0])
+    if canvas.dtype != torch.uint8 or not canvas.is_contiguous() or canvas.dim() != 4 or canvas.shape[3] != 3:
+        raise _C.GpnError("boxes_draw: canvas must be a contiguous [S,CH,CW,3] uint8 tensor")
+    if tuple(bbox.shape[1:]) != (8, 3) or box_scene.shape[0] != Q or trans.numel() != S * 4:
+        raise _C.GpnError("boxes_draw: bbox must be [Q,8,3], box_scene [Q] and trans [S,4]")
+    flat = [int(v) for rc in tiles for v in rc]
+    tiles_host = (_C.ctypes.c_int32 * max(len(flat), 1))(*flat)
+    L = _C.lib()
+    ws = _ws(L.gpn_boxes_draw_ws_bytes(i32(S), i32(H), i32(W)), dev)
+    check(L.gpn_boxes_draw(ptr(bbox), ptr(box_scene), i64(Q), ptr(trans), i32(S), i32(H), i32(W), *_cam(fx, fy, u0, v0),
+                           tiles_host, i32(len(tiles)), i32(edge), i32(canvas.shape[1]), i32(canvas.shape[2]), ptr(canvas),
+                           ptr(ws), szt(ws.numel()), _stream()), "gpn_boxes_draw")
+    return canvas
+
+
 # ---------------------------------------------------------------------------------------------------- C16
 # The opt-in bf16 INFERENCE ops (include/gpn.h section C16, csrc/spconv_bf16.hip): torch.bfloat16 tensors in and out, fp32
 # accumulation, one round-to-nearest-even per stored activation.  No autograd: an input that requires grad is an error.

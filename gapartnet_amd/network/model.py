@@ -92,6 +92,7 @@ class GAPartNet(LightningModule):
         super().__init__()
         self.save_hyperparameters()
         self.validation_step_outputs = []
+        self._visualize_outputs = []  # per loader, per test step: what the rendering of on_test_epoch_end needs (visualize only)
 
         self.in_channels = in_channels
         self.num_part_classes = num_part_classes
@@ -802,7 +803,63 @@ class GAPartNet(LightningModule):
                              num_points_per_instance=p.num_points_per_instance, sorted_indices=p.sorted_indices,
                              npcs_preds=p.npcs_preds, npcs_valid_mask=p.npcs_valid_mask)
         self._stash(dataloader_idx, (pc_ids, sem_seg, kept))
+        if self.visualize_cfg.get("visualize", False):
+            # what the rendering of on_test_epoch_end needs beyond the reference's 3-tuple: the scenes' real row counts and the
+            # proposal fields the kept Instances does not carry (a side list: the returned tuple stays the reference's)
+            extra = None
+            if kept is not None:
+                extra = Instances(valid_indices=p.valid_indices if p.valid_indices is not None
+                                  else torch.nonzero(p.valid_mask).squeeze(1))
+            while dataloader_idx > len(self._visualize_outputs) - 1:
+                self._visualize_outputs.append([])
+            if isinstance(point_clouds, PointCloudBatch):  # (a prepared batch: the scenes' rows are counted, one host read)
+                counts = torch.bincount(point_clouds.batch_indices.long(), minlength=point_clouds.batch_size).tolist()
+            else:
+                counts = [int(pc.points.shape[0]) for pc in point_clouds]
+            self._visualize_outputs[dataloader_idx].append((counts, extra))
         return pc_ids, sem_seg, kept
+
+    def _render_test_outputs(self) -> None:
+        """model.py:930-999: per split the sampled scenes' predictions as images (gapartnet_amd/misc/visu.py), batch by batch"""
+        import random
+        from ..misc import visu
+        cfg = self.visualize_cfg
+        self._resolve_pending_outputs()
+        for split, outputs, sides in zip(_SPLITS, self.validation_step_outputs, self._visualize_outputs):
+            if len(outputs) == 0:
+                continue
+            batch_of, row_of = [], []
+            for b, x in enumerate(outputs):
+                batch_of += [b] * len(x[0])
+                row_of += list(range(len(x[0])))
+            n = len(batch_of)
+            sample_num = int(cfg.get("sample_num", 0))
+            sample_ids = random.sample(range(n), sample_num) if sample_num > 0 else range(n)
+            by_batch = {}
+            for i in sample_ids:
+                by_batch.setdefault(batch_of[i], []).append(row_of[i])
+            for b, rows in sorted(by_batch.items()):
+                pc_ids, sem_seg, kept = outputs[b]
+                sizes, extra = sides[b]
+                off = [0]
+                for c in sizes:
+                    off.append(off[-1] + c)
+                sem_preds = sem_seg.sem_preds
+                dev = sem_preds.device
+                if kept is not None:
+                    kept.valid_indices = extra.valid_indices
+                    pred = visu.scene_predictions(kept, off)
+                    ins_map, npcs_map, bbox, box_scene = pred.ins_map, pred.npcs_map, pred.bbox, pred.box_scene
+                else:   # (the reference dereferences None here)
+                    ins_map = torch.zeros(off[-1], dtype=torch.int32, device=dev)
+                    npcs_map = torch.zeros((off[-1], 3), dtype=torch.float32, device=dev)
+                    bbox, box_scene = torch.zeros((0, 8, 3), dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+                visu.visualize_scenes(
+                    cfg["SAVE_ROOT"], cfg["GAPARTNET_DATA_ROOT"], cfg.get("RAW_IMG_ROOT", ""), cfg.get("save_option", []),
+                    [pc_ids[r] for r in rows], split, dev, [sem_preds[off[r]:off[r + 1]] for r in rows],
+                    [ins_map[off[r]:off[r + 1]] for r in rows], [npcs_map[off[r]:off[r + 1]] for r in rows],
+                    [bbox[box_scene == r] for r in rows], save_detail=bool(cfg.get("save_detail", False)))
+        self._visualize_outputs.clear()
 
     def _epoch_end_metrics(self) -> None:
         """semantic accuracy / mIoU and instance AP@50 / mAP(0.50:0.05:0.95) per split, plus the monitor_metrics means of
@@ -858,8 +915,7 @@ class GAPartNet(LightningModule):
 
     def on_test_epoch_end(self):
         if self.visualize_cfg.get("visualize", False):
-            print("[gapartnet_amd] visualisation / pose rendering of on_test_epoch_end is outside the accelerated hot "
-                  "path (SURVEY.md §2.1 #10) and is skipped; metrics are computed as in validation")
+            self._render_test_outputs()
         self._epoch_end_metrics()
 
     def configure_optimizers(self):

@@ -774,6 +774,70 @@ int gpn_pose_fit(const double* xyz, const double* npcs, const int64_t* offsets, 
                  size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * VS - test-time part predictions and the 3 x 4 panel of images per sampled scene (the reference's on_test_epoch_end,
+ * network/model.py:930-999, misc/visu.py, misc/visu_util.py).  Every "the last writer of the loop wins" of the reference is an
+ * integer atomicMax over the writer's position and a resolve pass: results are bit-reproducible and never depend on timing; no
+ * float atomics; no host read between the launches of an entry point.
+ * gpn_scene_maps: one batch's kept proposals -> per-point maps (model.py:954-971).  valid_indices [V] i64 = nonzero(valid_mask),
+ *   sorted_indices [M] i64, proposal_offsets [P+1] i64, npcs_valid_mask [M] u8, npcs_preds [Mv,3] f32 (row j belongs to the j-th
+ *   true entry of the mask), N rows in the batch.  The row of proposal point m is valid_indices[sorted_indices[m]].
+ *   ins_map [N] i32: 0 where no proposal, p + 1 for the points of proposal p; npcs_map [N,3] f32: zero, or the prediction of the
+ *   proposal point inside the mask that sits on the row; a row written by several m keeps the highest m (in both maps).
+ *   fit_npcs [M,3] f32 = npcs_map at each proposal point, minus 0.5 (a point outside the mask enters the fit as -0.5: kept quirk).
+ * gpn_points_winner: the geometry half of map2image (visu_util.py:107-139), once per scene for all its tiles.  xyz [n_total,3] f32
+ *   in the normalised frame, scene s = rows scene_offsets[s]:scene_offsets[s+1] (i64 [S+1], on the device), trans [S,4] f64 =
+ *   (r, cx, cy, cz) of the meta file.  In float64 without contraction: camera point = double(xyz) * r + c, u = rint(x * fx / z +
+ *   u0), v = rint(y * fy / z + v0) (half to even).  A point is dropped if u or v is not finite or v + 1 >= H, v < 0, u + 1 >= W,
+ *   u < 0 (-0.0 passes); a kept point covers (v,u), (v+1,u), (v+1,u+1), (v,u+1).  winner [S,H,W] i32 = the highest point index (in
+ *   its scene) covering the pixel, -1 where none.
+ * gpn_points_paint: all requested tiles of all scenes in one launch, into canvas [S,CH,CW,3] u8; tile (row, col) has its origin at
+ *   (edge + row * (H + edge), edge + col * (W + edge)).  A pixel without a winner is white.  Layer kinds (src is indexed by
+ *   scene_offsets[s] + winner):
+ *     GPN_VISU_RGB            src [n_total,3] f32: u8((src + offset) * 255.0f), float32, truncated toward zero; values outside
+ *                             [0, 256) are clamped to [0, 255] and NaN gives 0 (the reference's cast is undefined there)
+ *     GPN_VISU_LABEL          src [n_total] i32: palette[floormod(label, K)]
+ *     GPN_VISU_LABEL_MOD20    palette[floormod(label, 20)]
+ *     GPN_VISU_LABEL_MOD19P1  palette[floormod(label, 19) + 1], label -100 -> (230, 230, 230)
+ *     GPN_VISU_BLANK          white everywhere (src unused)
+ *   palette [K,3] u8 on the device (K >= 20 for the two modulo rules).
+ * gpn_boxes_draw: draw_bbox (visu_util.py:37-71) for all boxes of all scenes into the listed tiles (tiles_host [n_tiles,2] i32 =
+ *   (row, col), on the host).  bbox [Q,8,3] f64 in the normalised frame, box_scene [Q] i32.  Corner pixels by the projection rule
+ *   above.  The line rule (ours: OpenCV's is not restated): the all-integer Bresenham walk from a to b inclusive - dx = |x1 - x0|,
+ *   dy = -|y1 - y0|, err = dx + dy; each step plots the current pixel, stops at b, then with e2 = 2 err: e2 >= dy steps x and adds
+ *   dy to err, e2 <= dx steps y and adds dx to err - each plotted pixel stamped as a t x t square whose top-left is (x - t/2,
+ *   y - t/2); pixels outside the tile are dropped; an edge with a non-finite endpoint or one outside [-4W, 5W) x [-4H, 5H) is
+ *   skipped.  Per box GPN_VISU_BOX_DRAWS draws in the reference's order: the edges 0-1 0-2 0-3 1-4 1-5 2-6 6-3 4-7 5-7 3-5 2-4 6-7
+ *   in (255, 0, 255) with t = 2, then 0-1 (255, 0, 0), 0-3 (0, 0, 255), 0-2 (0, 255, 0) with t = 3 (colours as in the written
+ *   file).  The result equals drawing box by box and draw by draw in that order: a pixel keeps the highest q * 15 + e.
+ * ================================================================================================ */
+#define GPN_VISU_RGB 0
+#define GPN_VISU_LABEL 1
+#define GPN_VISU_LABEL_MOD20 2
+#define GPN_VISU_LABEL_MOD19P1 3
+#define GPN_VISU_BLANK 4
+#define GPN_VISU_MAX_LAYERS 16
+#define GPN_VISU_BOX_DRAWS 15
+typedef struct {
+  int32_t kind;    /* GPN_VISU_* */
+  int32_t row;     /* tile row */
+  int32_t col;     /* tile column */
+  float offset;    /* GPN_VISU_RGB: added before the scale */
+  const void* src; /* device pointer, see above */
+} gpn_visu_layer_t;
+size_t gpn_scene_maps_ws_bytes(int64_t N, int64_t M);
+int gpn_scene_maps(const int64_t* valid_indices, int64_t V, const int64_t* sorted_indices, const int64_t* proposal_offsets,
+                   int64_t P, const uint8_t* npcs_valid_mask, int64_t M, const float* npcs_preds, int64_t Mv, int64_t N,
+                   int32_t* ins_map, float* npcs_map, float* fit_npcs, void* ws, size_t ws_bytes, gpn_stream_t stream);
+int gpn_points_winner(const float* xyz, const int64_t* scene_offsets, int64_t n_total, const double* trans, int S, int H, int W,
+                      double fx, double fy, double u0, double v0, int32_t* winner, gpn_stream_t stream);
+int gpn_points_paint(const int32_t* winner, const int64_t* scene_offsets, int S, int H, int W, const gpn_visu_layer_t* layers_host,
+                     int n_layers, const uint8_t* palette, int K, int edge, int CH, int CW, uint8_t* canvas, gpn_stream_t stream);
+size_t gpn_boxes_draw_ws_bytes(int S, int H, int W);
+int gpn_boxes_draw(const double* bbox, const int32_t* box_scene, int64_t Q, const double* trans, int S, int H, int W, double fx,
+                   double fy, double u0, double v0, const int32_t* tiles_host, int n_tiles, int edge, int CH, int CW,
+                   uint8_t* canvas, void* ws, size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * DEV - entry points whose extents are DEVICE COUNTERS (round 4: the proposal stage of a training step without a host read;
  * reference glue: network/model.py:228-346, 348-462 - there every stage boundary is a device->host read of a size).
  * Convention of every *_dev entry point: an extent argument (N, P, M, V ...) is the BOUND its buffers are allocated for;
