@@ -45,6 +45,7 @@ const char* kEntryPoints[] = {
     "gpn_spconv_pack_weights_bf16", "gpn_spconv_fwd_bf16", "gpn_rows_to_bf16", "gpn_bn_act_bf16", "gpn_net_forward_bf16_ws_bytes",
     "gpn_net_forward_bf16",
     "gpn_scene_maps_ws_bytes", "gpn_scene_maps", "gpn_points_winner", "gpn_points_paint", "gpn_boxes_draw_ws_bytes", "gpn_boxes_draw",
+    "gpn_pointmlp_supported", "gpn_pointmlp_fwd", "gpn_pointmlp_wgrad_ws_bytes", "gpn_pointmlp_wgrad",
     "gpn_last_error", "gpn_version"};
 }  // namespace
 

@@ -3,6 +3,7 @@
   sparse_conv        — kernel C (forward / dgrad / wgrad) as one differentiable op
   gather_rows        — kernel G: voxel rows -> points, deterministic CSR transpose in backward
   segmented_maxpool  — kernel R (differentiable max-pool over proposal segments)
+  point_mlp          — section PM: one dense layer of the PointNet backbone over the scenes of a batch (PointSegments)
 """
 from typing import Optional
 
@@ -434,3 +435,78 @@ def bn_act(x: torch.Tensor, bn: torch.nn.BatchNorm1d, relu: bool, residual: Opti
         bn.num_batches_tracked.add_(1)
     return _BnActFn.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, float(bn.momentum),
                           float(bn.eps), bool(relu))
+
+
+class PointSegments:
+    """the scenes of a batch of points as the point-MLP kernels take them (csrc/pointmlp.hip): contiguous, non-empty row
+    ranges.  ``host`` = offsets [S + 1] as Python ints, ``offsets`` the same as int64 on the device, ``begin`` / ``end`` the
+    int32 form of the segmented pool / reduce operators."""
+
+    def __init__(self, counts, device):
+        self.counts = [int(c) for c in counts]
+        if not self.counts or min(self.counts) <= 0:
+            raise ValueError(f"every scene needs at least one point, got {self.counts}")
+        self.S = len(self.counts)
+        self.equal = len(set(self.counts)) == 1
+        self.host = [0]
+        for c in self.counts:
+            self.host.append(self.host[-1] + c)
+        self.N = self.host[-1]
+        if self.equal:  # made on the device: nothing to copy
+            self.offsets = torch.arange(self.S + 1, dtype=torch.int64, device=device) * self.counts[0]
+        else:
+            self.offsets = torch.as_tensor(self.host, dtype=torch.int64).to(device)
+        self.begin = self.offsets[:-1].to(torch.int32)
+        self.end = self.offsets[1:].to(torch.int32)
+
+
+class _PointMlpFn(torch.autograd.Function):
+    """y = x~ @ W_s^T + b + G[s] of the PointNet layers on the MFMA kernels of csrc/pointmlp.hip.  Backward: dx by the same
+    kernel on transposed weights, dW / db by the chunked MFMA reduction, dG by the segmented sum (kernel R)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, G, seg, view):
+        ops = backend.raw()
+        x, w = x.contiguous(), weight.detach().contiguous()
+        off, host = (seg.offsets, seg.host) if seg is not None else (None, None)
+        y, _ = ops.pointmlp_fwd(x, w, None if bias is None else bias.detach(), None if G is None else G.detach(), offsets=off,
+                                offsets_host=host, view=view)
+        ctx.save_for_backward(x, w)
+        ctx.seg, ctx.view, ctx.has_bias = seg, view, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ops = backend.raw()
+        x, w = ctx.saved_tensors
+        seg, view = ctx.seg, ctx.view
+        off, host = (seg.offsets, seg.host) if seg is not None else (None, None)
+        dy = dy.contiguous()
+        cin = w.shape[-1]
+        dx = dG = None
+        if ctx.needs_input_grad[0]:
+            dx, _ = ops.pointmlp_fwd(dy, w.transpose(-1, -2).contiguous(), offsets=off, offsets_host=host)
+            if view is not None:  # back into the flat array's own layout (equal scenes: the view's contract)
+                flat = torch.zeros_like(x)
+                sb, sc, sn = view
+                torch.as_strided(flat, (seg.S, seg.counts[0], cin), (sb, sn, sc)).copy_(dx.view(seg.S, seg.counts[0], cin))
+                dx = flat
+        dw, db = ops.pointmlp_wgrad(x, dy, cin, offsets=off, offsets_host=host, view=view, per_segment=w.dim() == 3,
+                                    need_dw=ctx.needs_input_grad[1], need_db=ctx.has_bias and ctx.needs_input_grad[2])
+        if ctx.needs_input_grad[3]:
+            dG = ops.segmented_reduce(dy, seg.begin, seg.end, "sum")
+        return dx, dw, db, dG, None, None
+
+
+def point_mlp_available(x: torch.Tensor, cin: int, cout: int) -> bool:
+    ops = backend.raw()
+    return (ops.name == "hip" and x.is_cuda and x.dtype == torch.float32 and hasattr(ops, "pointmlp_fwd")
+            and ops.pointmlp_supported(cin, cout))
+
+
+def point_mlp(x, weight, bias=None, G=None, seg: Optional[PointSegments] = None, view=None) -> torch.Tensor:
+    """one dense layer of the PointNet backbone over the rows of ``seg``'s scenes (None: one segment): ``weight`` [cout, cin]
+    or one matrix per scene [S, cout, cin] (the reference's torch.bmm with a predicted transform), ``G`` [S, cout] a per-scene
+    row added to every point of the scene (the scene-constant half of the 1088-wide concatenation), ``view`` = (sb, sc, sn)
+    when ``x`` is a flat array read as (scene, channel, point) - equal-sized scenes only."""
+    return _PointMlpFn.apply(x, weight, bias, G, seg, view)

@@ -1590,3 +1590,74 @@ def bn_act_bf16(x, weight, bias, running_mean, running_var, eps, relu, res=None)
                                    ptr(pars[2]), ptr(pars[3]), f32(eps), i64(N), i32(C), i32(1 if relu else 0), ptr(y), _stream()),
           "gpn_bn_act_bf16")
     return y
+
+
+# ---------------------------------------------------------------------------------------------------- PM (PointNet dense layers)
+def pointmlp_supported(cin: int, cout: int) -> bool:
+    return bool(_C.lib().gpn_pointmlp_supported(i32(cin), i32(cout)))
+
+
+def _host_offsets(offsets_host):
+    if offsets_host is None:
+        return None
+    return (_C.ctypes.c_int64 * len(offsets_host))(*[int(v) for v in offsets_host])
+
+
+def _pointmlp_x(x, view, N, cin, offsets_host):
+    """-> (strided, sb, sc, sn) of gpn_pointmlp_*'s X~; a strided ``view`` = (sb, sc, sn) over the flat array ``x`` is checked
+    against the array's size here (the kernels trust it), which takes the host copy of the offsets"""
+    if view is None:
+        assert x.dim() == 2 and x.shape == (N, cin), (tuple(x.shape), N, cin)
+        return 0, 0, 0, 0
+    sb, sc, sn = (int(v) for v in view)
+    if offsets_host is None or min(sb, sc, sn) < 0:
+        raise _C.GpnError("a strided point-MLP input needs the host copy of the segment offsets and non-negative strides")
+    longest = max(offsets_host[s + 1] - offsets_host[s] for s in range(len(offsets_host) - 1))
+    if (len(offsets_host) - 2) * sb + (cin - 1) * sc + (longest - 1) * sn >= x.numel():
+        raise _C.GpnError("the strided point-MLP view reaches past its array")
+    return 1, sb, sc, sn
+
+
+def pointmlp_fwd(x, weight, bias=None, G=None, scale=None, shift=None, relu=False, offsets=None, offsets_host=None, view=None,
+                 want_y=True, want_max=False):
+    """epi(x~ W_s^T + bias + G[s]) of csrc/pointmlp.hip -> (Y [N, cout] or None, M [S, cout] or None).  ``weight`` [cout, cin] or
+    [S, cout, cin]; ``offsets`` [S + 1] int64 on the device (None: one segment); ``view`` = (sb, sc, sn): x is a flat array
+    read as (segment, channel, point)."""
+    dev = _dev(x, weight)
+    x, weight = _c(x, torch.float32), _c(weight, torch.float32)
+    per_segment = weight.dim() == 3
+    cout, cin = weight.shape[-2:]
+    S = 1 if offsets is None else offsets.shape[0] - 1
+    assert not per_segment or weight.shape[0] == S
+    if offsets is not None:
+        assert offsets.dtype == torch.int64 and offsets.is_cuda
+        offsets = offsets.contiguous()
+    N = x.shape[0] if view is None else int(offsets_host[-1])
+    strided, sb, sc, sn = _pointmlp_x(x, view, N, cin, offsets_host)
+    bias, G, scale, shift = (_c(t, torch.float32) for t in (bias, G, scale, shift))
+    assert G is None or G.shape == (S, cout)
+    y = torch.empty((N, cout), dtype=torch.float32, device=dev) if want_y else None
+    m = torch.empty((S, cout), dtype=torch.float32, device=dev) if want_max else None
+    check(_C.lib().gpn_pointmlp_fwd(ptr(x), i32(strided), i64(sb), i64(sc), i64(sn), ptr(weight), i32(per_segment), ptr(bias), ptr(G),
+                                    ptr(scale), ptr(shift), i32(bool(relu)), ptr(offsets), _host_offsets(offsets_host), i64(S), i64(N),
+                                    i32(cin), i32(cout), ptr(y), ptr(m), _stream()), "gpn_pointmlp_fwd")
+    return y, m
+
+
+def pointmlp_wgrad(x, dy, cin, offsets=None, offsets_host=None, view=None, per_segment=False, need_dw=True, need_db=False):
+    """-> (dW [cout, cin] or [S, cout, cin] = dy^T x~, db [cout] = column sums of dy), either None when not needed"""
+    dev = _dev(x, dy)
+    x, dy = _c(x, torch.float32), _c(dy, torch.float32)
+    N, cout = dy.shape
+    S = 1 if offsets is None else offsets.shape[0] - 1
+    strided, sb, sc, sn = _pointmlp_x(x, view, N, cin, offsets_host)
+    dw = torch.empty(((S, cout, cin) if per_segment else (cout, cin)), dtype=torch.float32, device=dev) if need_dw else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if need_db else None
+    if not (need_dw or need_db):
+        return None, None
+    L = _C.lib()
+    ws = _ws(L.gpn_pointmlp_wgrad_ws_bytes(i64(N), i64(S), i32(cin), i32(cout)), dev)
+    check(L.gpn_pointmlp_wgrad(ptr(x), i32(strided), i64(sb), i64(sc), i64(sn), ptr(dy), ptr(offsets), _host_offsets(offsets_host),
+                               i64(S), i64(N), i32(cin), i32(cout), i32(bool(per_segment)), ptr(dw), ptr(db), ptr(ws), szt(ws.numel()),
+                               _stream()), "gpn_pointmlp_wgrad")
+    return dw, db

@@ -130,3 +130,24 @@ class SparseUNet(nn.Module):
                 spconv.SubMConv3d(in_channels, channels[0], kernel_size=3, padding=1, bias=False, indice_key="subm1"),
                 norm_fn(channels[0]), nn.ReLU())
         return cls(stem, UBlock(channels, ResBlock, block_repeat, norm_fn, indice_key_id=1))
+
+
+class PointNetBackbone(nn.Module):
+    """the reference's dense backbone (network/backbone.py:284-297): ``self.backbone`` = PointNetSegBackbone, so the keys under
+    the model are ``backbone.backbone.feat.stn.conv1.weight`` and so on.  The executor-only features of the sparse U-Net (the
+    native layer-program executor, bf16 inference, the coarse-level row counts of the collate) do not apply to it."""
+
+    def __init__(self, pc_dim: int, feature_dim: int):
+        super().__init__()
+        from .pointnet import PointNetSegBackbone
+        self.pc_dim = pc_dim
+        self.feature_dim = feature_dim
+        self.backbone = PointNetSegBackbone(self.pc_dim, self.feature_dim)
+
+    def forward(self, input_pc):
+        """input_pc [B, 3 + pc_dim, N] -> ([B, N, feature_dim], {}) as in the reference"""
+        return self.backbone(input_pc), {}
+
+    def forward_points(self, points, counts, layout: str = "reference"):
+        """the batch's row-major point array [sum N, 3 + pc_dim] with ``counts`` points per scene -> [sum N, feature_dim]"""
+        return self.backbone.forward_rows(points, counts, layout)

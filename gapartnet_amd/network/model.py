@@ -88,6 +88,10 @@ class GAPartNet(LightningModule):
         # (SparseUNet.inference_dtype); None = fp32 everywhere.  The ScoreNet / NPCS-Net U-Nets (paired passes, device-counted
         # rows) stay fp32 either way.
         inference_dtype: Optional[torch.dtype] = None,
+        # not in the reference: how the PointNet backbone reads the row-major point array.  "reference" = the reference's
+        # points.reshape(-1, 6, N), a reinterpretation (not a transpose) that its checkpoints were trained with - equal-sized
+        # scenes only; "points" = every point its own six values, ragged batches allowed
+        pointnet_input_layout: str = "reference",
     ):
         super().__init__()
         self.save_hyperparameters()
@@ -135,14 +139,21 @@ class GAPartNet(LightningModule):
         self.score_scale = instance_seg_cfg["score_scale"]
 
         norm_fn = functools.partial(nn.BatchNorm1d, eps=1e-4, momentum=0.1)
-        if self.backbone_type != "SparseUNet":
-            raise NotImplementedError(
-                f"backbone type {self.backbone_type!r}: only the SparseUNet path is on the accelerated hot path "
-                "(the dense PointNet backbone of the reference is out of scope, SURVEY.md §2.1 #9)")
         channels = self.backbone_cfg["channels"]
         block_repeat = self.backbone_cfg["block_repeat"]
-        width = channels[0]
-        self.backbone = SparseUNet.build(in_channels, channels, block_repeat, norm_fn)
+        if self.backbone_type == "SparseUNet":
+            width = channels[0]
+            self.backbone = SparseUNet.build(in_channels, channels, block_repeat, norm_fn)
+        elif self.backbone_type == "PointNet":  # (model.py:93-99 of the reference)
+            from .backbone import PointNetBackbone
+            from .pointnet.pointnet_utils import LAYOUTS
+            if pointnet_input_layout not in LAYOUTS:
+                raise ValueError(f"pointnet_input_layout must be one of {LAYOUTS}, got {pointnet_input_layout!r}")
+            width = self.backbone_cfg["feature_dim"]
+            self.backbone = PointNetBackbone(self.backbone_cfg["pc_dim"], width)
+        else:
+            raise NotImplementedError(f"backbone type {self.backbone_type!r} not implemented")
+        self.pointnet_input_layout = pointnet_input_layout
         self.inference_dtype = inference_dtype
         self.sem_seg_head = nn.Linear(width, self.num_part_classes)
         self.offset_head = nn.Sequential(nn.Linear(width, width), norm_fn(width), nn.ReLU(inplace=True),
@@ -168,14 +179,24 @@ class GAPartNet(LightningModule):
     def inference_dtype(self):
         """None (fp32) or torch.bfloat16: the number format of the BACKBONE's inference passes (SparseUNet.inference_dtype).  The
         ScoreNet / NPCS-Net U-Nets stay fp32."""
-        return self.backbone.inference_dtype
+        return getattr(self.backbone, "inference_dtype", None)
 
     @inference_dtype.setter
     def inference_dtype(self, value):
+        if self.backbone_type != "SparseUNet":
+            if value is not None:
+                raise ValueError(f"inference_dtype={value!r}: the reduced-precision inference path belongs to the SparseUNet "
+                                 f"backbone; the {self.backbone_type} backbone runs in fp32 (pass None)")
+            return
         self.backbone.inference_dtype = value
 
     # ------------------------------------------------------------------------------------------ forward pieces
     def forward_backbone(self, pc_batch: PointCloudBatch) -> torch.Tensor:
+        if self.backbone_type == "PointNet":  # (model.py:154-156 of the reference, N = the batch's points per scene)
+            counts = pc_batch.scene_counts
+            if counts is None:
+                counts = torch.bincount(pc_batch.batch_indices.long(), minlength=pc_batch.batch_size).tolist()
+            return self.backbone.forward_points(pc_batch.points, counts, self.pointnet_input_layout)
         voxel_features = self.backbone(pc_batch.voxel_tensor)
         return GF.gather_rows(voxel_features.features, pc_batch.pc_voxel_id, getattr(pc_batch, "pc_voxel_csr", None))
 

@@ -48,6 +48,30 @@ size_t gpn_linear_bwd_ws_bytes(int64_t N, int cin, int cout);
 int gpn_linear_bwd(const float* x, const float* W, const float* dy, int64_t N, int cin, int cout, float* dx, float* dW, float* db,
                    void* ws, size_t ws_bytes, gpn_stream_t stream);
 
+/* ---- PM: dense point-MLP layers of the PointNet backbone on the fp32 MFMA (csrc/pointmlp.hip) -------------------------------
+ * Replaces the Conv1d(k = 1) / Linear layers, the two torch.bmm and the max over points of network/pointnet/pointnet_utils.py
+ * and pointnet_sem_seg.py.  Forward, for rows r < N of fp32 data in S contiguous, non-empty segments (offsets [S + 1] i64 on
+ * the device; NULL with S == 1 = one segment; offsets_host = the caller's host copy or NULL, checked when given):
+ *     Y[r, :] = epi( X~[r, :] . W_s(r)^T + b + G[s(r), :] )
+ *   X~  row-major [N, cin] (strided == 0), or the view (segment b, channel c, point n of the segment) -> x[b sb + c sc + n sn]
+ *   W   [cout, cin] (per_segment == 0) or [S, cout, cin]; b [cout] and G [S, cout] optional
+ *   epi y -> epi_scale[c] y + epi_shift[c] (both or neither), then max(0, .) if relu
+ *   Y   [N, cout] or NULL;  M [S, cout] or NULL = per-segment column maxima of the same values (deterministic); one of the
+ *       two at least.  With Y == NULL the layer's output is never written.
+ * No row tile mixes two segments.  dgrad (dX = dY W_s) is this call on transposed weights.
+ * wgrad: dW [cout, cin] (or [S, cout, cin]) = dY^T X~ and db [cout] = column sums of dY (either may be NULL), reduced over
+ * fixed row chunks on the MFMA and summed in chunk order: deterministic, no float atomics.
+ * 1 <= cin <= 4096, 1 <= cout <= 8192 (gpn_pointmlp_supported); N == 0 is GPN_OK. */
+int gpn_pointmlp_supported(int cin, int cout);
+int gpn_pointmlp_fwd(const float* x, int strided, int64_t sb, int64_t sc, int64_t sn, const float* W, int per_segment,
+                     const float* b, const float* G, const float* epi_scale, const float* epi_shift, int relu,
+                     const int64_t* offsets, const int64_t* offsets_host, int64_t S, int64_t N, int cin, int cout, float* Y,
+                     float* M, gpn_stream_t stream);
+size_t gpn_pointmlp_wgrad_ws_bytes(int64_t N, int64_t S, int cin, int cout);
+int gpn_pointmlp_wgrad(const float* x, int strided, int64_t sb, int64_t sc, int64_t sn, const float* dy, const int64_t* offsets,
+                       const int64_t* offsets_host, int64_t S, int64_t N, int cin, int cout, int per_segment, float* dW,
+                       float* db, void* ws, size_t ws_bytes, gpn_stream_t stream);
+
 /* ---- optional in-library kernel timing (hipEvent pairs around launches; used by bench.py) ------- */
 /* kernel ids for gpn_prof_get */
 enum {
@@ -59,7 +83,8 @@ enum {
   GPN_K_CCL = 5,
   GPN_K_BN = 6, /* BatchNorm passes (statistics where not taken by a conv epilogue, apply forward / backward) */
   GPN_K_LINEAR = 7, /* the dense heads (section H) */
-  GPN_K_COUNT = 8
+  GPN_K_POINTMLP = 8, /* the PointNet backbone's dense layers (section PM): forward / dgrad and wgrad launches */
+  GPN_K_COUNT = 9
 };
 /* fixed cost of a (start event, launch, stop event) bracket, measured around an empty kernel on `stream` (median, us):
  * subtract it from hipEvent-measured launch durations before comparing them with a profiler's kernel durations. */
