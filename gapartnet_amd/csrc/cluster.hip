@@ -155,7 +155,8 @@ __global__ void ccl_hook_kernel(const int32_t* __restrict__ begin_end, const int
     // they do not climb to the root at all
     const int32_t pv = uf_load(parent + v);
     const bool same = uf_load(parent + u) == pv;
-    if (__builtin_amdgcn_ballot_w64(!same) == 0) continue;
+    const uint64_t same_lanes = __builtin_amdgcn_ballot_w64(same);
+    if (same_lanes == ~0ull) continue;
     const int32_t r = uf_find(parent, same ? (int32_t)v : u);
     int32_t m = r;
 #pragma unroll
@@ -171,6 +172,10 @@ __global__ void ccl_hook_kernel(const int32_t* __restrict__ begin_end, const int
       if (lane == leader) uf_union(parent, rl, m);
       todo &= ~__builtin_amdgcn_ballot_w64(r == rl);
     }
+    // the vertex itself is represented by the lanes that are `same` (padding lanes included).  A full chunk of 64 edges
+    // none of which shares the vertex's parent has no such lane: its neighbours were joined to m, the vertex was not -
+    // a one-sided graph (the neighbours' rows do not name the vertex) then stayed split
+    if (same_lanes == 0 && lane == 0) uf_union(parent, uf_find(parent, (int32_t)v), m);
   }
 }
 

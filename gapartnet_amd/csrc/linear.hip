@@ -296,7 +296,14 @@ static int linear_bwd_impl(const float* x, const float* W, const float* dy, int6
     GPN_CHECK_ARG(x);
     float* partial = static_cast<float*>(ws);
     const int tile_rows = (size_t)kTileRows * (cin + cout + 1) * sizeof(float) <= 65536 ? kTileRows : kTileRows / 2;
-    const size_t lds = (size_t)tile_rows * (cin + cout + 1) * sizeof(float);  // 22 KB for a 16 -> 27 head
+    size_t lds = (size_t)tile_rows * (cin + cout + 1) * sizeof(float);  // 22 KB for a 16 -> 27 head
+    // the kernel reuses the allocation as red[G][owners][5] when it runs row groups: for cin = 4, cout <= 4 that scratch
+    // (5 * G * owners = 1275-1280 floats) is larger than the tiles (768-1152 floats)
+    const int owners = cout * (cin / 4);
+    if (owners <= kThreads / 2) {
+      const size_t red = (size_t)5 * (kThreads / owners) * owners * sizeof(float);
+      if (red > lds) lds = red;
+    }
     hipLaunchKernelGGL(linear_dw_partial_kernel, dim3(blocks), dim3(kThreads), lds, stream, x, dy, N, cin, cout, tile_rows, partial,
                        rows.dev);
     GPN_CHECK_LAUNCH();
