@@ -1395,6 +1395,84 @@ def view_convert(depth, rgb, sem, ins, npcs, K, m, max_groups=0):
     return buf, layout
 
 
+# ---------------------------------------------------------------------------------------------------- CP (raw clouds)
+CLOUD_OK, CLOUD_FEW, CLOUD_EMPTY, CLOUD_DEGENERATE = 0, 1, 2, 3
+
+
+def _cloud_args(points, offsets):
+    """points [M, C] f32 whose rows may be a column slice of a wider array (unit stride inside a row), offsets [S+1] known on
+    the host -> (points, row pitch in floats, host offsets list, device offsets i64)"""
+    dev = _dev(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3:
+        raise _C.GpnError(f"clouds must be float32 [M, C >= 3], got {points.dtype} {tuple(points.shape)}")
+    if points.shape[0] > 0 and (points.stride(1) != 1 or points.stride(0) < points.shape[1]):
+        points = points.contiguous()
+    pitch = int(points.stride(0)) if points.shape[0] > 1 else int(points.shape[1])
+    host = [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    if len(host) < 1 or host[0] != 0 or host[-1] != points.shape[0] or any(b < a for a, b in zip(host[:-1], host[1:])):
+        raise _C.GpnError("cloud offsets must rise from 0 to the number of rows")
+    return points, pitch, host, torch.tensor(host, dtype=torch.int64).to(dev, non_blocking=True)
+
+
+def cloud_prepare(points, offsets, m, max_groups=0):
+    """S ragged raw clouds -> the network's input (include/gpn.h section CP): gpn_cloud_pack, gpn_view_fps, gpn_cloud_finish, no
+    host read between them and ONE at the end (counts, status, scale).  points [M, C >= 3] f32 (xyz first; rows with a
+    non-finite coordinate are skipped), offsets [S+1] on the host.
+    -> dict: out [S, m, C] f32 (ball-normalised xyz + the other columns; rows past counts[s] zero), sample_rows [S, m] i32 (-1 past
+    counts[s]), offsets (device i64), and on the host counts [S] i64 = min(valid rows, m), status [S] i64, scale [S, 4] f64."""
+    points, pitch, host, off_dev = _cloud_args(points, offsets)
+    dev = points.device
+    S, M, C, m = len(host) - 1, int(points.shape[0]), int(points.shape[1]), int(m)
+    nb = max(max((b - a for a, b in zip(host[:-1], host[1:])), default=1), 1)
+    packed = torch.empty((S, nb, 4), dtype=torch.float32, device=dev)
+    rows = torch.empty((S, nb), dtype=torch.int32, device=dev)
+    # counts, status and scale share one buffer: one copy to the host
+    tail = torch.zeros((S, 6), dtype=torch.float64, device=dev)
+    ints = tail[:, 4:].view(torch.int32)  # [S, 4] i32: column 0 counts, column 1 status
+    counts, status = torch.empty((S,), dtype=torch.int32, device=dev), torch.empty((S,), dtype=torch.int32, device=dev)
+    out = torch.empty((S, m, C), dtype=torch.float32, device=dev)
+    sample_rows = torch.empty((S, m), dtype=torch.int32, device=dev)
+    scale = torch.empty((S, 4), dtype=torch.float64, device=dev)
+    L = _C.lib()
+    if S > 0:
+        check(L.gpn_cloud_pack(ptr(points), i64(M), i32(pitch), ptr(off_dev), i32(S), i64(nb), ptr(packed), ptr(rows), ptr(counts),
+                               ptr(status), _stream()), "gpn_cloud_pack")
+        idx = view_fps(packed, counts, status, m, max_groups)
+        check(L.gpn_cloud_finish(ptr(points), i64(M), i32(pitch), i32(C), ptr(off_dev), i32(S), i64(nb), ptr(rows), ptr(counts), ptr(idx),
+                                 i32(m), ptr(status), ptr(out), ptr(sample_rows), ptr(scale), _stream()), "gpn_cloud_finish")
+        tail[:, :4] = scale
+        ints[:, 0] = counts
+        ints[:, 1] = status
+    host_tail = tail.cpu()
+    host_ints = host_tail[:, 4:].view(torch.int32)
+    return dict(out=out, sample_rows=sample_rows, offsets=off_dev, counts_dev=counts, status_dev=status,
+                counts=host_ints[:, 0].long().clamp(max=m), status=host_ints[:, 1].long(), scale=host_tail[:, :4].clone())
+
+
+def cloud_nearest(points, offsets, sample_rows, counts, status, want_d2=False):
+    """for every row of the caller's clouds the nearest sample of its own cloud, exact (include/gpn.h section CP): points [M, C] f32,
+    offsets [S+1] (host), sample_rows [S, m] i32, counts / status [S] i32 on the device (the valid-row counts and statuses of
+    cloud_prepare) -> nn [M] i32 = the sample's position in its cloud, -1 for invalid rows and clouds that are not OK
+    (, d2 [M] f32)"""
+    points, pitch, host, off_dev = _cloud_args(points, offsets)
+    dev = _dev(points, sample_rows, counts, status)
+    S, M = len(host) - 1, int(points.shape[0])
+    sample_rows, counts, status = _c(sample_rows, torch.int32), _c(counts, torch.int32), _c(status, torch.int32)
+    if sample_rows.dim() != 2 or sample_rows.shape[0] != S or counts.shape[0] != S or status.shape[0] != S:
+        raise _C.GpnError("cloud_nearest: sample_rows must be [S, m], counts and status [S]")
+    m = int(sample_rows.shape[1])
+    nn = torch.empty((M,), dtype=torch.int32, device=dev)
+    d2 = torch.empty((M,), dtype=torch.float32, device=dev) if want_d2 else None
+    if S > 0 and M > 0:
+        L = _C.lib()
+        ws = _ws(L.gpn_cloud_nearest_ws_bytes(i32(S), i32(m)), dev)
+        check(L.gpn_cloud_nearest(ptr(points), i64(M), i32(pitch), ptr(off_dev), i32(S), ptr(sample_rows), ptr(counts), ptr(status),
+                                  i32(m), ptr(nn), ptr(d2), ptr(ws), szt(ws.numel()), _stream()), "gpn_cloud_nearest")
+    else:
+        nn.fill_(-1)
+    return (nn, d2) if want_d2 else nn
+
+
 # ---------------------------------------------------------------------------------------------------- VS (test-time rendering)
 VISU_RGB, VISU_LABEL, VISU_LABEL_MOD20, VISU_LABEL_MOD19P1, VISU_BLANK = 0, 1, 2, 3, 4
 VISU_MAX_LAYERS = 16

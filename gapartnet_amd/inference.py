@@ -1,0 +1,437 @@
+"""Label-free inference on raw point clouds: from a cloud to parts and part boxes (reference: the deployment entry points
+gapartnet/tools/visu.py:79-143 ``_inference_perception_model`` / ``inference_real`` and structure/utils.py:118-192; its CPU front
+end tools/visu_utils.py:141-173 ``OBJfile2points`` / ``FindMaxDis`` / ``WorldSpaceToBallSpace``).
+
+``prepare_clouds``   ragged raw clouds of any size, sensor NaNs included -> the network's input: valid rows, FPS down to
+                     ``num_points``, ball normalisation over the sampled points (csrc/cloudprep.hip; include/gpn.h section CP)
+``PartPredictor``    ``model(pcs)`` -> score filter + NMS -> per-point maps and one box per part (the kernels of the test epoch's
+                     rendering) -> every row of the caller's cloud through its nearest sampled point (gpn_cloud_nearest)
+``read_obj_points``  the reference's OBJ reader
+``python -m gapartnet_amd.inference --ckpt X --input a.npy b.obj ... --out DIR [--num_points N] [--inference_dtype bf16]
+        [--panels] [--no_flip]``
+
+CUDA tensors run on the HIP library; CPU tensors take the same graph in torch ops (FPS as a plain loop) - for tests and tiny
+inputs, never chosen for a CUDA tensor.
+"""
+import argparse
+import os
+from dataclasses import dataclass
+from typing import Callable, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from .hip_ops import CLOUD_DEGENERATE, CLOUD_EMPTY, CLOUD_OK  # (include/gpn.h section CP; importing loads no library)
+from .misc.pose_fitting_batched import estimate_pose_from_npcs_batched
+from .structure.point_cloud import PointCloud
+
+STATUS_NAMES = {CLOUD_OK: "ok", CLOUD_EMPTY: "empty", CLOUD_DEGENERATE: "degenerate"}
+
+
+@dataclass
+class PreparedClouds:
+    points: torch.Tensor        # [sum m_s, C] f32: ball-normalised xyz + the caller's other columns, the OK clouds' samples in order
+    counts: torch.Tensor        # [S] i64 (host): m_s = min(valid rows, num_points) of an OK cloud, 0 otherwise
+    sample_rows: torch.Tensor   # [sum m_s] i64: the row of every sample inside its caller's cloud
+    scale: torch.Tensor         # [S, 4] f64 (host): (r, cx, cy, cz) - caller's frame = normalised * r + c
+    status: torch.Tensor        # [S] i64 (host): CLOUD_OK / CLOUD_EMPTY / CLOUD_DEGENERATE
+    offsets: List[int]          # [S+1]: the clouds' rows in ``source``
+    source: torch.Tensor        # [M, C] f32: the caller's clouds, concatenated
+    table: Optional[dict] = None  # device tables gpn_cloud_nearest reads (CUDA only)
+
+
+# ---------------------------------------------------------------------------------------------------- torch formulation (CPU)
+def _fps_loop(xyz: np.ndarray, m: int) -> np.ndarray:
+    """pointnet2's furthest point sampling on one cloud as a plain loop (float32, start 0): per "thread" t of a block of
+    B = largest power of two <= n (at most 1024) the first maximum over k = t, t + B, ..., then the block's tree reduction in which the
+    lower thread wins a tie - the order csrc/viewprep.hip's fps_better states in closed form"""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    n = xyz.shape[0]
+    B = min(1 << (int(n).bit_length() - 1), 1024)
+    rows = (n + B - 1) // B
+    t = np.full(n, 1e10, dtype=np.float32)
+    out = np.zeros(m, dtype=np.int64)
+    pad = np.full(rows * B, -1.0, dtype=np.float32)
+    old = 0
+    for j in range(1, m):
+        d = xyz - xyz[old]
+        dd = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        t = np.minimum(t, dd)
+        pad[:n] = t
+        grid = pad.reshape(rows, B)
+        first = grid.argmax(0)  # (first maximum: the lowest k of the thread)
+        val, idx = grid[first, np.arange(B)], first * B + np.arange(B)
+        s = B // 2
+        while s >= 1:
+            v1, v2, i1, i2 = val[:s], val[s:2 * s], idx[:s], idx[s:2 * s]
+            idx = np.where(v2 > v1, i2, i1)
+            val = np.maximum(v1, v2)
+            s //= 2
+        old = int(idx[0])
+        out[j] = old
+    return out
+
+
+def _prepare_cloud_torch(cloud: torch.Tensor, m: int):
+    """one cloud -> (status, normalised [m_s, C] f32, sample_rows [m_s] i64, scale [4] f64)"""
+    C = cloud.shape[1]
+    none = (torch.zeros((0, C), dtype=torch.float32), torch.zeros(0, dtype=torch.int64), torch.zeros(4, dtype=torch.float64))
+    rows = torch.nonzero(torch.isfinite(cloud[:, :3]).all(1)).squeeze(1)
+    n = int(rows.shape[0])
+    if n == 0:
+        return (CLOUD_EMPTY,) + none
+    if n > m:
+        rows = rows[torch.from_numpy(_fps_loop(cloud[rows, :3].numpy(), m))]
+    p = cloud[rows, :3].double()
+    c = (p.max(0)[0] + p.min(0)[0]) / 2
+    d = p - c
+    r = torch.sqrt(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).max())
+    scale = torch.cat([r[None], c])
+    if not bool(r > 0):
+        return CLOUD_DEGENERATE, none[0], none[1], scale
+    out = cloud[rows].clone()
+    out[:, :3] = (d / r).float()
+    return CLOUD_OK, out, rows, scale
+
+
+def _nearest_torch(queries: torch.Tensor, samples: torch.Tensor, chunk: int = 4096) -> torch.Tensor:
+    """[n] i64: per query the nearest sample, fp32 (dx*dx + dy*dy) + dz*dz, lowest index on ties; -1 for a non-finite query"""
+    n, ms = queries.shape[0], samples.shape[0]
+    nn = torch.full((n,), -1, dtype=torch.int64, device=queries.device)
+    if ms == 0:
+        return nn
+    ar = torch.arange(ms, device=queries.device)
+    for a in range(0, n, chunk):
+        q = queries[a:a + chunk]
+        dx, dy, dz = (q[:, None, k] - samples[None, :, k] for k in range(3))
+        d = (dx * dx + dy * dy) + dz * dz
+        best = torch.where(d == d.amin(1, keepdim=True), ar[None, :], ms).amin(1)
+        nn[a:a + chunk] = torch.where(torch.isfinite(q).all(1), best, -1)
+    return nn
+
+
+# ---------------------------------------------------------------------------------------------------- front end
+def _check_clouds(clouds: Sequence[torch.Tensor]):
+    clouds = [torch.as_tensor(c) for c in clouds]
+    if not clouds:
+        raise ValueError("no clouds given")
+    C, dev = clouds[0].shape[-1], clouds[0].device
+    for c in clouds:
+        if c.dim() != 2 or c.shape[1] != C or C < 3 or c.dtype != torch.float32 or c.device != dev:
+            raise ValueError("clouds must be float32 tensors [N_i, C] with one C >= 3 on one device")
+    return clouds
+
+
+def prepare_clouds(clouds: Sequence[torch.Tensor], num_points: int = 20000, max_groups: int = 0) -> PreparedClouds:
+    """``clouds``: [N_i, C] float32 tensors, xyz first, any N_i (0 included); rows with a non-finite coordinate are skipped.  A cloud
+    with more than ``num_points`` valid rows is sampled by FPS, a smaller one keeps every valid row; centre and radius of the ball
+    normalisation are those of the SAMPLED points, as in the converter the training data came from."""
+    clouds = _check_clouds(clouds)
+    m = int(num_points)
+    if m < 1:
+        raise ValueError("num_points must be positive")
+    offsets = [0]
+    for c in clouds:
+        offsets.append(offsets[-1] + int(c.shape[0]))
+    source = torch.cat(clouds, 0)
+    if source.is_cuda:
+        from . import backend
+        hip = backend.raw()
+        if hip.name != "hip":
+            raise RuntimeError("prepare_clouds on GPU tensors needs the HIP library as the operator backend")
+        got = hip.cloud_prepare(source, offsets, m, max_groups)
+        status = got["status"]
+        counts = torch.where(status == CLOUD_OK, got["counts"], torch.zeros_like(got["counts"]))
+        S = len(clouds)
+        # (the live slots of the [S, m] tables, listed on the host from the counts it already holds: no second host read)
+        live = torch.arange(m)[None, :] < counts[:, None]
+        take = torch.nonzero(live.reshape(-1)).squeeze(1).to(source.device, non_blocking=True)
+        points = got["out"].reshape(S * m, -1).index_select(0, take)
+        sample_rows = got["sample_rows"].reshape(-1).index_select(0, take).long()
+        table = dict(sample_rows=got["sample_rows"], counts=got["counts_dev"], status=got["status_dev"])
+        return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, source, table)
+    parts = [_prepare_cloud_torch(c, m) for c in clouds]
+    return PreparedClouds(torch.cat([p[1] for p in parts]), torch.tensor([p[1].shape[0] for p in parts], dtype=torch.int64),
+                          torch.cat([p[2] for p in parts]), torch.stack([p[3] for p in parts]),
+                          torch.tensor([p[0] for p in parts], dtype=torch.int64), offsets, source)
+
+
+def nearest_samples(prep: PreparedClouds) -> torch.Tensor:
+    """[M] i64: for every row of the caller's clouds the position (inside its cloud's samples) of the nearest sampled point, in the
+    caller's coordinates; -1 for invalid rows and for clouds that are not OK"""
+    if prep.source.is_cuda:
+        from . import backend
+        t = prep.table
+        return backend.raw().cloud_nearest(prep.source, prep.offsets, t["sample_rows"], t["counts"], t["status"]).long()
+    out, first = [], 0
+    for s, ms in enumerate(prep.counts.tolist()):
+        cloud = prep.source[prep.offsets[s]:prep.offsets[s + 1], :3]
+        out.append(_nearest_torch(cloud, cloud[prep.sample_rows[first:first + ms]]))
+        first += ms
+    return torch.cat(out)
+
+
+# ---------------------------------------------------------------------------------------------------- predictions
+@dataclass
+class PartPrediction:
+    status: int                     # CLOUD_OK / CLOUD_EMPTY / CLOUD_DEGENERATE; everything below is empty / -1 unless OK
+    scale: torch.Tensor             # [4] f64: (r, cx, cy, cz)
+    sem: torch.Tensor               # [N] i64: part class of every row (0 = no part), -1 on invalid rows
+    instance: torch.Tensor          # [N] i64: position (in proposal_scores) of the kept proposal the row belongs to, -1 where none
+    npcs: torch.Tensor              # [N, 3] f32 (zero where no proposal)
+    proposal_scores: torch.Tensor   # [P] f32
+    proposal_classes: torch.Tensor  # [P] i64
+    bbox: torch.Tensor              # [Q, 8, 3] f64 in the caller's frame
+    box_proposal: torch.Tensor      # [Q] i64: the proposal of every box
+    # the network's own view of the cloud (what the panels show)
+    sample_rows: torch.Tensor       # [m] i64
+    sampled_points: torch.Tensor    # [m, C] f32, normalised frame
+    sampled_sem: torch.Tensor       # [m] i64
+    sampled_instance: torch.Tensor  # [m] i64
+    sampled_npcs: torch.Tensor      # [m, 3] f32
+    bbox_normalised: torch.Tensor   # [Q, 8, 3] f64
+
+    def to_numpy(self) -> dict:
+        return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items()}
+
+
+def scene_maps_torch(valid_indices, sorted_indices, proposal_offsets, npcs_valid_mask, npcs_preds, n_rows):
+    """gpn_scene_maps in torch ops (include/gpn.h section VS): a row written by several proposal points keeps the highest"""
+    dev = sorted_indices.device
+    M = sorted_indices.shape[0]
+    rows = valid_indices[sorted_indices]
+    po = proposal_offsets.long()
+    ar = torch.arange(M, device=dev)
+    pid = torch.searchsorted(po[1:].contiguous(), ar, right=True)
+    winner = torch.full((n_rows,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, rows, ar, "amax")
+    hit = winner >= 0
+    w = winner.clamp(min=0)
+    ins_map = torch.where(hit, pid[w] + 1, 0).to(torch.int32) if M else torch.zeros(n_rows, dtype=torch.int32, device=dev)
+    npcs_map = torch.zeros((n_rows, 3), dtype=torch.float32, device=dev)
+    if M:
+        mask = npcs_valid_mask.bool()
+        slot = (mask.long().cumsum(0) - 1).clamp(min=0)
+        inside = hit & mask[w]
+        npcs_map = torch.where(inside[:, None], npcs_preds[slot[w]] if npcs_preds.shape[0] else npcs_map, npcs_map)
+    return ins_map, npcs_map, npcs_map[rows] - 0.5
+
+
+def _scene_predictions(kept, scene_offsets, picks, max_iters):
+    """misc.visu.scene_predictions on the GPU; the same steps in torch ops for CPU tensors"""
+    from .misc import visu
+    if kept.sorted_indices.is_cuda:
+        return visu.scene_predictions(kept, scene_offsets, picks=picks, max_iters=max_iters)
+    off = torch.as_tensor(scene_offsets, dtype=torch.int64)
+    po = kept.proposal_offsets.long()
+    ins_map, npcs_map, fit_npcs = scene_maps_torch(kept.valid_indices, kept.sorted_indices, po, kept.npcs_valid_mask,
+                                                   kept.npcs_preds, int(off[-1]))
+    P = po.shape[0] - 1
+    empty = torch.zeros(0, dtype=torch.int64)
+    if P <= 0:
+        return visu.ScenePredictions(ins_map, npcs_map, torch.zeros((0, 8, 3), dtype=torch.float64), empty, empty, off)
+    fit = estimate_pose_from_npcs_batched(kept.pt_xyz, fit_npcs, po, picks=picks, max_iters=max_iters)
+    keep = ((po[1:] - po[:-1]) >= 10) & fit["valid"]
+    box_proposal = torch.nonzero(keep).squeeze(1)
+    box_scene = kept.batch_indices.index_select(0, po[:-1]).long().index_select(0, box_proposal)
+    return visu.ScenePredictions(ins_map, npcs_map, fit["bbox"].index_select(0, box_proposal), box_scene, box_proposal, off)
+
+
+Picks = Union[None, torch.Tensor, Callable[[List[int]], torch.Tensor]]
+
+
+class PartPredictor:
+    """``predict(clouds)``: raw clouds in, per cloud the parts of EVERY row and one 9-DoF box per part in the caller's frame.
+    ``picks``: the RANSAC draws of the box fits - None (drawn from numpy's global generator), a tensor [kept proposals,
+    max_iters, 5], or a callable taking the kept proposals' sizes (in batch order) and returning that tensor."""
+
+    def __init__(self, model, num_points: int = 20000, max_iters: int = 100):
+        self.model, self.num_points, self.max_iters = model.eval(), int(num_points), int(max_iters)
+
+    def _empty(self, n: int, C: int, status: int, scale, dev) -> PartPrediction:
+        i64, f32 = torch.int64, torch.float32
+        z = lambda *shape, dtype=i64: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+        return PartPrediction(status=status, scale=scale, sem=torch.full((n,), -1, dtype=i64, device=dev),
+                              instance=torch.full((n,), -1, dtype=i64, device=dev), npcs=z(n, 3, dtype=f32),
+                              proposal_scores=z(0, dtype=f32), proposal_classes=z(0), bbox=z(0, 8, 3, dtype=torch.float64),
+                              box_proposal=z(0), sample_rows=z(0), sampled_points=z(0, C, dtype=f32), sampled_sem=z(0),
+                              sampled_instance=z(0), sampled_npcs=z(0, 3, dtype=f32), bbox_normalised=z(0, 8, 3, dtype=torch.float64))
+
+    @torch.no_grad()
+    def predict(self, clouds: Sequence[torch.Tensor], picks: Picks = None) -> List[PartPrediction]:
+        model = self.model
+        prep = prepare_clouds(clouds, self.num_points)
+        C = prep.source.shape[1]
+        if C < model.in_channels:
+            raise ValueError(f"the model reads {model.in_channels} columns per point, the clouds have {C}")
+        dev = prep.source.device
+        S = len(prep.offsets) - 1
+        counts = prep.counts.tolist()
+        net_off = [0]
+        for c in counts:
+            net_off.append(net_off[-1] + c)
+        ok = [s for s in range(S) if counts[s] > 0]
+        out = [self._empty(prep.offsets[s + 1] - prep.offsets[s], C, int(prep.status[s]), prep.scale[s], dev) for s in range(S)]
+        if not ok:
+            return out
+        pcs = [PointCloud(pc_id=str(s), points=prep.points[net_off[s]:net_off[s + 1], :model.in_channels].contiguous(), obj_cat=0)
+               for s in ok]
+        _, sem_seg, proposals = model(pcs)
+        n_net = net_off[-1]
+        sem = sem_seg.sem_preds.long()
+        ins = torch.full((n_net,), -1, dtype=torch.int64, device=dev)
+        npcs = torch.zeros((n_net, 3), dtype=torch.float32, device=dev)
+        kept = pred = None
+        if proposals is not None:
+            kept = model._post_process_kept_points(proposals)
+            sizes = kept.proposal_offsets[1:] - kept.proposal_offsets[:-1]
+            if callable(picks):
+                picks = picks(sizes.tolist())
+            # (scene k of the network's batch is the k-th OK cloud; the clouds that are not OK own no rows)
+            pred = _scene_predictions(kept, [net_off[s] for s in ok] + [n_net], picks, self.max_iters)
+            ins, npcs = pred.ins_map.long() - 1, pred.npcs_map
+        # every row of the caller's clouds through its nearest sampled point
+        nn = nearest_samples(prep)
+        first = torch.repeat_interleave(torch.tensor(net_off[:-1], dtype=torch.int64).to(dev),
+                                        torch.tensor([b - a for a, b in zip(prep.offsets[:-1], prep.offsets[1:])]).to(dev),
+                                        output_size=prep.offsets[-1])
+        hit = nn >= 0
+        g = (first + nn).clamp(min=0, max=max(n_net - 1, 0))
+        sem_all = torch.where(hit, sem[g], -1)
+        ins_all = torch.where(hit, ins[g], -1)
+        npcs_all = torch.where(hit[:, None], npcs[g], torch.zeros_like(npcs[g]))
+        if kept is not None:
+            P = kept.score_preds.shape[0]
+            prop_scene = kept.batch_indices.index_select(0, kept.proposal_offsets[:-1].long()).long()  # [P], in the OK clouds' numbering
+            # position of every proposal among its own scene's proposals
+            local = torch.zeros(P, dtype=torch.int64, device=dev)
+            for k in range(len(ok)):
+                mine = prop_scene == k
+                local = torch.where(mine, mine.long().cumsum(0) - 1, local)
+            local_pad = torch.cat([local, local.new_full((1,), -1)])
+            # (the scene of every proposal and of every box in ONE copy to the host: the clouds' slices are listed there)
+            scene_host = torch.cat([prop_scene, pred.box_scene.long()]).cpu()
+            prop_scene_host, box_scene_host = scene_host[:P], scene_host[P:]
+        for k, s in enumerate(ok):
+            a, b = prep.offsets[s], prep.offsets[s + 1]
+            na, nb = net_off[s], net_off[s + 1]
+            o = out[s]
+            o.sem, o.npcs = sem_all[a:b], npcs_all[a:b]
+            o.sample_rows, o.sampled_points = prep.sample_rows[na:nb], prep.points[na:nb]
+            o.sampled_sem, o.sampled_npcs = sem[na:nb], npcs[na:nb]
+            o.instance, o.sampled_instance = ins_all[a:b], ins[na:nb]
+            if kept is None:
+                continue
+            o.instance, o.sampled_instance = local_pad[ins_all[a:b]], local_pad[ins[na:nb]]
+            mine = torch.nonzero(prop_scene_host == k).squeeze(1).to(dev, non_blocking=True)
+            o.proposal_scores = kept.score_preds.index_select(0, mine)
+            o.proposal_classes = kept.pt_sem_classes.index_select(0, mine).long()
+            boxes = torch.nonzero(box_scene_host == k).squeeze(1).to(dev, non_blocking=True)
+            o.bbox_normalised = pred.bbox.index_select(0, boxes)
+            sc = prep.scale[s].to(dev)
+            o.bbox = o.bbox_normalised * sc[0] + sc[1:]
+            o.box_proposal = local[pred.box_proposal.index_select(0, boxes)]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------- files and the command line
+def read_obj_points(path: str) -> np.ndarray:
+    """the reference's OBJfile2points (tools/visu_utils.py:141-155): every line ``v x y z r g b`` up to the first ``vt`` line
+    -> float64 [n, 6]"""
+    points = []
+    with open(path) as fh:
+        for line in fh:
+            strs = line.split(" ")
+            if strs[0] == "v":
+                points.append(tuple(float(v) for v in strs[1:7]))
+            if strs[0] == "vt":
+                break
+    return np.array(points)
+
+
+def load_model(ckpt: str, device, inference_dtype: Optional[str] = None):
+    """a checkpoint as gapartnet_amd.trainer writes it ({"state_dict", "hyper_parameters"}) -> GAPartNet in eval mode"""
+    from .network.model import GAPartNet
+    ck = torch.load(ckpt, map_location="cpu", weights_only=False)
+    args = dict(ck["hyper_parameters"])
+    args["ckpt"] = ""
+    args["inference_dtype"] = torch.bfloat16 if inference_dtype == "bf16" else None
+    model = GAPartNet(**args)
+    model.load_state_dict(ck["state_dict"])
+    return model.to(device).eval()
+
+
+def _read_cloud(path: str, flip: bool) -> np.ndarray:
+    if path.endswith(".obj"):
+        pts = read_obj_points(path)
+        if flip:  # tools/visu.py:150-151
+            pts[:, 2] = -pts[:, 2]
+            pts[:, 1] = -pts[:, 1]
+        return pts.astype(np.float32)
+    if path.endswith(".npy"):
+        return np.load(path).astype(np.float32)
+    raise ValueError(f"{path}: inputs are .npy arrays [N, C >= 3] or .obj files with `v x y z r g b` lines")
+
+
+def _write_panels(preds: Sequence[PartPrediction], names: Sequence[str], out_dir: str):
+    """the prediction tiles of the test epoch's panel (misc/visu.render_panels) over the sampled points of every OK cloud"""
+    from .misc import visu
+    rows = [(n, p) for n, p in zip(names, preds) if p.status == CLOUD_OK]
+    if not rows:
+        return []
+    dev = rows[0][1].sampled_points.device
+    off = np.concatenate([[0], np.cumsum([p.sampled_points.shape[0] for _, p in rows])]).astype(np.int64)
+    xyz = torch.cat([p.sampled_points[:, :3] for _, p in rows]).contiguous()
+    rgb = torch.cat([p.sampled_points[:, 3:6] if p.sampled_points.shape[1] >= 6 else torch.full_like(p.sampled_points[:, :3], 0.6)
+                     for _, p in rows]).contiguous()
+    options = ("pc", "sem_pred", "ins_pred", "npcs_pred", "bbox_pred", "bbox_pred_pure")
+    canvas = visu.render_panels(
+        xyz, rgb, off, torch.stack([p.scale for _, p in rows]).to(dev),
+        sem_pred=torch.cat([p.sampled_sem for _, p in rows]).int(), ins_pred=torch.cat([p.sampled_instance + 1 for _, p in rows]).int(),
+        npcs_pred=torch.cat([p.sampled_npcs for _, p in rows]).contiguous(),
+        bbox_pred=torch.cat([p.bbox_normalised for _, p in rows]),
+        bbox_pred_scene=torch.cat([torch.full((p.bbox.shape[0],), k, dtype=torch.int32, device=dev) for k, (_, p) in enumerate(rows)]),
+        options=options).cpu().numpy()
+    from PIL import Image
+    paths = []
+    for k, (name, _) in enumerate(rows):
+        paths.append(os.path.join(out_dir, name + ".png"))
+        Image.fromarray(canvas[k]).save(paths[-1], compress_level=1)
+    return paths
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m gapartnet_amd.inference", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--ckpt", required=True)
+    ap.add_argument("--input", nargs="+", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--num_points", type=int, default=20000)
+    ap.add_argument("--inference_dtype", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--panels", action="store_true")
+    ap.add_argument("--no_flip", action="store_true", help="keep the y and z signs of .obj inputs")
+    ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
+    args = ap.parse_args(argv)
+    device = torch.device(args.device)
+    if args.panels and device.type != "cuda":
+        ap.error("--panels renders on the GPU (misc/visu.render_panels): it cannot be combined with --device cpu")
+    model = load_model(args.ckpt, device, args.inference_dtype)
+    clouds = [torch.from_numpy(_read_cloud(p, not args.no_flip)).to(device) for p in args.input]
+    names = [os.path.splitext(os.path.basename(p))[0] for p in args.input]
+    os.makedirs(args.out, exist_ok=True)
+    # (one batch per column count: a batch shares its C)
+    preds: List[Optional[PartPrediction]] = [None] * len(clouds)
+    predictor = PartPredictor(model, num_points=args.num_points)
+    for C in sorted({int(c.shape[1]) for c in clouds}):
+        ids = [i for i, c in enumerate(clouds) if c.shape[1] == C]
+        for i, p in zip(ids, predictor.predict([clouds[i] for i in ids])):
+            preds[i] = p
+    for name, p in zip(names, preds):
+        np.savez(os.path.join(args.out, name + ".npz"), **p.to_numpy())
+        print(f"{name}: {STATUS_NAMES.get(p.status, p.status)}, {p.sem.shape[0]} rows, {p.proposal_scores.shape[0]} parts, "
+              f"{p.bbox.shape[0]} boxes")
+    if args.panels:
+        _write_panels(preds, names, args.out)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

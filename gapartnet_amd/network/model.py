@@ -704,6 +704,52 @@ class GAPartNet(LightningModule):
             self.log(key, value, batch_size=batch_size, on_epoch=True, prog_bar=False, logger=True, sync_dist=True)
         return data_batch.pc_ids, sem_seg, proposals, loss
 
+    # ------------------------------------------------------------------------------------------ label-free inference
+    @staticmethod
+    def _without_labels(pc: PointCloud) -> PointCloud:
+        return PointCloud(pc_id=pc.pc_id, points=pc.points, obj_cat=pc.obj_cat, voxel_features=pc.voxel_features,
+                          voxel_coords=pc.voxel_coords, voxel_coords_range=pc.voxel_coords_range, pc_voxel_id=pc.pc_voxel_id)
+
+    @torch.no_grad()
+    def forward(self, point_clouds: Union[Sequence[PointCloud], PointCloudBatch]):
+        """``model(pcs)`` on clouds WITHOUT labels (the reference's deployment call, tools/visu.py:79-143, structure/utils.py:118-192)
+        -> (pc_ids, Segmentation, Instances or None).  Labels a cloud may carry are not read.  The epoch gates count as passed
+        (the reference sets them to 0 before inference, tools/visu.py:70-72); no loss, no IoU against ground truth, nothing logged.
+        Instances: the fields of proposal_clustering_and_revoxelize(instance_labels=None) plus
+        ``score_preds`` [P] = sigmoid(score_logits[p, sem_preds[first point of p] - 1]), ``npcs_preds`` [M,3] = for EVERY proposal
+        point the triple of its predicted class, ``npcs_valid_mask`` [M] all true.  The proposal stage runs in its form with host
+        reads (the reads of a call); the training steps' proposal plan is left alone."""
+        if not isinstance(point_clouds, PointCloudBatch):
+            point_clouds = [self._without_labels(pc) for pc in point_clouds]
+        data_batch = self._collate(point_clouds)
+        saved = (self._want_npcs_preds, self.sync_free_proposals, self._prop_gate)
+        self._want_npcs_preds, self.sync_free_proposals = True, False
+        try:
+            pt_xyz = data_batch.points[:, :3]
+            pc_feature = self.forward_backbone(pc_batch=data_batch)
+            sem_logits = self.forward_sem_seg(pc_feature)
+            offsets_preds = self.forward_offset(pc_feature)
+            sem_preds = torch.argmax(sem_logits, dim=-1)
+            sem_seg = Segmentation(batch_size=data_batch.batch_size, sem_preds=sem_preds)
+            voxel_tensor, pc_voxel_id, proposals = self.proposal_clustering_and_revoxelize(
+                pt_xyz=pt_xyz, batch_indices=data_batch.batch_indices, pt_features=pc_feature, sem_preds=sem_preds,
+                offset_preds=offsets_preds, instance_labels=None, batch_size=data_batch.batch_size)
+            if proposals is None:
+                return data_batch.pc_ids, sem_seg, None
+            pair = self.forward_proposal_unets(voxel_tensor)
+            score_feats, npcs_feats = pair if pair is not None else (None, None)
+            score_logits = self.forward_proposal_score(voxel_tensor, pc_voxel_id, proposals, score_feats)
+            cls = proposals.sem_preds.long()
+            proposal_cls = cls[proposals.proposal_offsets[:-1].long()]
+            proposals.score_preds = score_logits.gather(1, proposal_cls[:, None] - 1).squeeze(1).sigmoid()
+            npcs_logits = self.forward_proposal_npcs(voxel_tensor, pc_voxel_id, npcs_feats, None)
+            per_class = npcs_logits.reshape(npcs_logits.shape[0], npcs_logits.shape[1] // 3, 3)
+            proposals.npcs_preds = per_class.gather(1, (cls - 1)[:, None, None].expand(-1, 1, 3)).squeeze(1)
+            proposals.npcs_valid_mask = torch.ones((cls.shape[0],), dtype=torch.bool, device=cls.device)
+            return data_batch.pc_ids, sem_seg, proposals
+        finally:
+            self._want_npcs_preds, self.sync_free_proposals, self._prop_gate = saved
+
     # ------------------------------------------------------------------------------------------ Lightning hooks
     def training_step(self, point_clouds, batch_idx: int):
         return self._training_or_validation_step(point_clouds, batch_idx, "train")[3]
@@ -759,17 +805,44 @@ class GAPartNet(LightningModule):
         and ~25 reads.  Works on exactly-sized and on device-counted proposals.  None: not applicable (no member_slot - the
         unfused proposal path - or a table overflow inside the kernel): the caller runs the torch formulation.
         ``defer``: -> a ``_PendingKept`` whose ``resolve()`` does the read (and the re-indexing) later."""
-        slot = getattr(proposals, "member_slot", None)
-        if slot is None or proposals.score_preds is None or proposals.point_indices is None:
+        if not self._post_process_rows_apply(proposals):
             return None
-        dev = proposals.dev_counts
-        out = backend.raw().proposals_postprocess(
-            proposals.score_preds, proposals.num_points_per_proposal, proposals.proposal_offsets, proposals.point_indices,
-            proposals.proposal_indices, slot, self.val_score_threshold, self.val_min_num_points_per_proposal,
-            self.val_nms_iou_threshold, rows=dev["P"] if dev is not None else None, defer=defer)
+        out = self._post_process_rows(proposals, defer)
         if defer:
             return _PendingKept(self, proposals, out)
         return self._kept_from(proposals, out)
+
+    @staticmethod
+    def _post_process_rows_apply(proposals: Instances) -> bool:
+        return not (getattr(proposals, "member_slot", None) is None or proposals.score_preds is None
+                    or proposals.point_indices is None)
+
+    def _post_process_rows(self, proposals: Instances, defer: bool = False):
+        """the library call of ``_post_process_kept``: (kept ids, new offsets, source row of every kept proposal point), None after a
+        table overflow, or the handle of a deferred read"""
+        dev = proposals.dev_counts
+        return backend.raw().proposals_postprocess(
+            proposals.score_preds, proposals.num_points_per_proposal, proposals.proposal_offsets, proposals.point_indices,
+            proposals.proposal_indices, proposals.member_slot, self.val_score_threshold, self.val_min_num_points_per_proposal,
+            self.val_nms_iou_threshold, rows=dev["P"] if dev is not None else None, defer=defer)
+
+    def _post_process_kept_points(self, proposals: Instances) -> Instances:
+        """label-free inference: what ``_post_process_kept`` keeps, WITH the per-point fields of the kept proposals that
+        misc.visu.scene_predictions reads (every proposal point carries an NPCS prediction there: ``GAPartNet.forward``).  The
+        torch formulation where the fused call does not apply (oracle backend, unfused proposal stage, table overflow)."""
+        out = self._post_process_rows(proposals) if self._post_process_rows_apply(proposals) else None
+        if out is None:
+            p = self._post_process(proposals)
+            if p.valid_indices is None:
+                p.valid_indices = torch.nonzero(p.valid_mask).squeeze(1)
+            return p
+        kept = self._kept_from(proposals, out)
+        ids, _, src_row = out
+        kept.valid_indices = proposals.valid_indices
+        kept.num_points_per_proposal = proposals.num_points_per_proposal.index_select(0, ids)
+        for f in ("sorted_indices", "point_indices", "pt_xyz", "sem_preds", "npcs_preds", "npcs_valid_mask"):
+            setattr(kept, f, getattr(proposals, f).index_select(0, src_row))
+        return kept
 
     @staticmethod
     def _kept_from(proposals: Instances, out) -> Optional[Instances]:
@@ -780,7 +853,8 @@ class GAPartNet(LightningModule):
         return Instances(score_preds=proposals.score_preds.index_select(0, ids),
                          pt_sem_classes=proposals.sem_preds.index_select(0, first),
                          batch_indices=proposals.batch_indices.index_select(0, src_row),
-                         instance_sem_labels=proposals.instance_sem_labels, ious=proposals.ious.index_select(0, ids),
+                         instance_sem_labels=proposals.instance_sem_labels,
+                         ious=proposals.ious.index_select(0, ids) if proposals.ious is not None else None,  # (label-free: none)
                          proposal_offsets=new_offsets, valid_mask=proposals.valid_mask)
 
     def _stash(self, dataloader_idx: int, item) -> None:

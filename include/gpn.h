@@ -784,6 +784,48 @@ int gpn_view_finish(const void* depth, int depth_bytes, const uint8_t* rgb, cons
                     double* scale, gpn_stream_t stream);
 
 /* ================================================================================================
+ * CP - label-free inference on raw point clouds: S ragged clouds -> the network's input, and per-sample predictions -> every row.
+ * What the reference does on the CPU around `perception_model(pcs)` (tools/visu_utils.py:157-173 FindMaxDis / WorldSpaceToBallSpace,
+ * structure/utils.py:345,613 FPS), plus what it has no answer for: the points that were not sampled.
+ * points [M, stride] f32 with xyz in columns 0..2 (stride >= 3 = the row pitch in floats: a column slice of a wider array passes
+ * the wide array's; gpn_cloud_finish takes the slice's own column count as `cols` <= stride),
+ * offsets [S+1] i64 on the device: cloud s = rows offsets[s]:offsets[s+1].  A row is VALID when its three coordinates are finite.
+ * gpn_cloud_pack: per cloud the valid rows in ascending row order (a scan, no atomic counter) -> packed [S, n_bound, 4] f32 = .xyz
+ *   and .w = 1e10 (exactly what gpn_view_backproject writes: the layout gpn_view_fps reads), rows [S, n_bound] i32 = the row inside
+ *   the caller's cloud, counts [S] i32, status [S] i32 = GPN_CLOUD_OK, or GPN_CLOUD_EMPTY when no row is valid.  n_bound >= the
+ *   largest cloud's row count (rows past it are ignored).
+ * Sampling is gpn_view_fps(packed, n_bound, counts, status, S, m, ...) as it is: GPN_CLOUD_OK == GPN_VIEW_OK, a cloud with
+ *   counts[s] > m is sampled, == m gives arange, and < m is flagged GPN_CLOUD_FEW (== GPN_VIEW_TOO_FEW) with no indices written,
+ *   which gpn_cloud_finish reads as "keep every valid point".
+ * gpn_cloud_finish: per cloud over its m_s = min(counts[s], m) samples, in float64 from the caller's float32 rows: c = (max + min)
+ *   / 2, r = sqrt(max((dx*dx + dy*dy) + dz*dz)), xyz = float32((p - c) / r) - the formula of gpn_view_finish.  DECISION: centre and
+ *   radius are taken over the SAMPLED points, not the whole cloud - that is what the converter (section VP) does and so what the
+ *   network was trained on.  out [S, m, cols] f32 = normalised xyz, the other columns copied bit for bit (rows past m_s zero),
+ *   sample_rows [S, m] i32 = the caller's row (inside its cloud) of every sample (-1 past m_s), scale [S, 4] f64 = (r, cx, cy, cz).
+ *   status: GPN_CLOUD_FEW becomes GPN_CLOUD_OK; r == 0 (one point, or all equal) sets GPN_CLOUD_DEGENERATE (xyz written as 0).
+ * gpn_cloud_nearest: for every one of the M rows (sampled or not) the nearest sample of its own cloud, in the caller's coordinates:
+ *   d2 = (dx*dx + dy*dy) + dz*dz in fp32 without fma (the convention of gpn_ball_query), ties to the lowest sample.  nn [M] i32 = the
+ *   sample's position 0 .. m_s - 1 in its cloud; -1 for an invalid row, for every row of a cloud whose status is not GPN_CLOUD_OK
+ *   and for rows outside [offsets[0], offsets[S]).  d2_out [M] f32 (may be NULL): that distance, +inf where nn is -1.  EXACT: a
+ *   per-cloud uniform grid over the samples' box (at most 64 cells an axis; histogram, scan, stable scatter), each query walks
+ *   Chebyshev rings of cells around its own (clamped) cell and stops when no unvisited ring can hold an equal or nearer sample;
+ *   after 3 rings it scans all samples of the cloud (queries far outside the box, all samples in one cell).
+ * ================================================================================================ */
+#define GPN_CLOUD_OK 0
+#define GPN_CLOUD_FEW 1
+#define GPN_CLOUD_EMPTY 2
+#define GPN_CLOUD_DEGENERATE 3
+int gpn_cloud_pack(const float* points, int64_t M, int stride, const int64_t* offsets, int S, int64_t n_bound, float* packed,
+                   int32_t* rows, int32_t* counts, int32_t* status, gpn_stream_t stream);
+int gpn_cloud_finish(const float* points, int64_t M, int stride, int cols, const int64_t* offsets, int S, int64_t n_bound,
+                     const int32_t* rows, const int32_t* counts, const int32_t* idx, int m, int32_t* status, float* out,
+                     int32_t* sample_rows, double* scale, gpn_stream_t stream);
+size_t gpn_cloud_nearest_ws_bytes(int S, int m);
+int gpn_cloud_nearest(const float* points, int64_t M, int stride, const int64_t* offsets, int S, const int32_t* sample_rows,
+                      const int32_t* counts, const int32_t* status, int m, int32_t* nn, float* d2_out, void* ws, size_t ws_bytes,
+                      gpn_stream_t stream);
+
+/* ================================================================================================
  * PF - pose fitting.  replaces the per-proposal numpy loop of gapartnet/misc/pose_fitting.py:4-147 (estimate_pose_from_npcs:
  * 5-point RANSAC over Umeyama similarity fits, Umeyama on the inliers, NPCS-aligned box; callers network/model.py:966-980,
  * structure/utils.py:172-188) for ALL proposals of a batch: two launches, float64 like the reference.
