@@ -47,6 +47,7 @@ const char* kEntryPoints[] = {
     "gpn_scene_maps_ws_bytes", "gpn_scene_maps", "gpn_points_winner", "gpn_points_paint", "gpn_boxes_draw_ws_bytes", "gpn_boxes_draw",
     "gpn_pointmlp_supported", "gpn_pointmlp_fwd", "gpn_pointmlp_wgrad_ws_bytes", "gpn_pointmlp_wgrad",
     "gpn_cloud_pack", "gpn_cloud_finish", "gpn_cloud_nearest_ws_bytes", "gpn_cloud_nearest",
+    "gpn_mask_pack", "gpn_proposals_from_masks_ws_bytes", "gpn_proposals_from_masks",
     "gpn_last_error", "gpn_version"};
 }  // namespace
 

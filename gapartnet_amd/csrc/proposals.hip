@@ -674,6 +674,44 @@ int revoxelize(const float* scaled, const int32_t* proposal_offsets, int64_t* co
   return GPN_OK;
 }
 
+// The stage behind the proposal tables, shared by gpn_proposals_build and gpn_proposals_from_masks: per-proposal frame, scaled
+// coordinates, re-voxelisation into fullscale^3 grids, [V,4] rows, rows of the grid's coarse level.  T2 = capacity of the
+// per-point tables, P_ub = capacity of the per-proposal ones; counts[kM] / counts[kP] hold the live sizes on the device.
+int proposal_tail(const float* pt_xyz_p, const int64_t* proposal_indices, const int32_t* proposal_offsets, int64_t* counts,
+                  const float* jitter, float fullscale, float max_scale, int64_t T2, int64_t P_ub, float* mean, float* scale,
+                  float* shift, float* scaled, float* rmin, float* rmax, float* vf, int64_t* seg64, int32_t* vc3, int32_t* vseg,
+                  int32_t* rv_nvox, int32_t* rv_nout, int32_t* rv_vbase, int32_t* rv_kbase, int32_t* rv_obase, void* sub,
+                  size_t sub_bytes, int32_t* voxel_coords4, int32_t* pc_voxel_id, int32_t* point_order, int32_t* voxel_point_start,
+                  hipStream_t stream) {
+  hipLaunchKernelGGL(prop_stats_kernel, dim3((int)gpn::cdiv(P_ub, kThreads / 64)), dim3(kThreads), 0, stream, pt_xyz_p,
+                     proposal_offsets, counts, jitter, fullscale, 1.0f / fullscale, max_scale, mean, scale, shift);
+  GPN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(prop_scale_points_kernel, dim3(grid_of(T2)), dim3(kThreads), 0, stream, pt_xyz_p, proposal_indices, counts,
+                     mean, scale, shift, T2, scaled);
+  GPN_CHECK_LAUNCH();
+  if (revox_fits(fullscale)) {
+    int rc = revoxelize(scaled, proposal_offsets, counts, T2, P_ub, fullscale, vc3, vseg, pc_voxel_id, point_order,
+                        voxel_point_start, rv_nvox, rv_nout, rv_vbase, rv_kbase, rv_obase, stream);
+    if (rc) return rc;
+  } else {
+    hipLaunchKernelGGL(prop_ranges_kernel, dim3(grid_of(P_ub * 3)), dim3(kThreads), 0, stream, P_ub, fullscale, rmin, rmax);
+    GPN_CHECK_LAUNCH();
+    const float vs[3] = {1.0f, 1.0f, 1.0f};
+    const int32_t dims[3] = {(int32_t)fullscale + 1, (int32_t)fullscale + 1, (int32_t)fullscale + 1};
+    int rc = gpn_voxelize_ex(scaled, scaled, seg64, rmin, rmax, T2, 3, P_ub, vs, dims, vf, vc3, vseg, pc_voxel_id,
+                             counts + kV, point_order, voxel_point_start, sub, sub_bytes, (gpn_stream_t)stream);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(prop_finish_kernel, dim3(grid_of(T2)), dim3(kThreads), 0, stream, vc3, vseg, pc_voxel_id, T2,
+                     voxel_coords4, counts);
+  GPN_CHECK_LAUNCH();
+  // rows of the proposal grid's coarse level (the ScoreNet / NPCS-Net U-Nets have one stride-2 level): with it in the same
+  // read as the other counts, building their rulebooks needs no host read of its own
+  const int32_t grid_shape[3] = {(int32_t)fullscale, (int32_t)fullscale, (int32_t)fullscale};
+  return gpn_rulebook_level_counts(voxel_coords4, T2, counts + kV, P_ub > 0 ? P_ub : 1, grid_shape, 1, counts + kCoarse, sub, sub_bytes,
+                                   (gpn_stream_t)stream);
+}
+
 }  // namespace
 
 extern "C" int64_t gpn_proposals_max_proposals(int64_t N, int min_points) {
@@ -774,34 +812,9 @@ extern "C" int gpn_proposals_build(const float* points, int point_stride, const 
                      proposal_offsets, o.seg64, counts);
   GPN_CHECK_LAUNCH();
 
-  // ---- per-proposal frame, scaled coordinates, re-voxelisation into fullscale^3 grids
-  hipLaunchKernelGGL(prop_stats_kernel, dim3((int)gpn::cdiv(P_ub, kThreads / 64)), dim3(kThreads), 0, stream, pt_xyz_p,
-                     proposal_offsets, counts, jitter, fullscale, 1.0f / fullscale, max_scale, o.mean, o.scale, o.shift);
-  GPN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(prop_scale_points_kernel, dim3(grid_of(T2)), dim3(kThreads), 0, stream, pt_xyz_p, proposal_indices, counts,
-                     o.mean, o.scale, o.shift, T2, o.scaled);
-  GPN_CHECK_LAUNCH();
-  if (revox_fits(fullscale)) {
-    int rc = revoxelize(o.scaled, proposal_offsets, counts, T2, P_ub, fullscale, o.vc3, o.vseg, pc_voxel_id, point_order,
-                        voxel_point_start, o.rv_nvox, o.rv_nout, o.rv_vbase, o.rv_kbase, o.rv_obase, stream);
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(prop_ranges_kernel, dim3(grid_of(P_ub * 3)), dim3(kThreads), 0, stream, P_ub, fullscale, o.rmin, o.rmax);
-    GPN_CHECK_LAUNCH();
-    const float vs[3] = {1.0f, 1.0f, 1.0f};
-    const int32_t dims[3] = {(int32_t)fullscale + 1, (int32_t)fullscale + 1, (int32_t)fullscale + 1};
-    int rc = gpn_voxelize_ex(o.scaled, o.scaled, o.seg64, o.rmin, o.rmax, T2, 3, P_ub, vs, dims, o.vf, o.vc3, o.vseg, pc_voxel_id,
-                             counts + kV, point_order, voxel_point_start, o.sub, o.sub_bytes, stream_);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(prop_finish_kernel, dim3(grid_of(T2)), dim3(kThreads), 0, stream, o.vc3, o.vseg, pc_voxel_id, T2,
-                     voxel_coords4, counts);
-  GPN_CHECK_LAUNCH();
-  // rows of the proposal grid's coarse level (the ScoreNet / NPCS-Net U-Nets have one stride-2 level): with it in the same
-  // read as the other counts, building their rulebooks needs no host read of its own
-  const int32_t grid_shape[3] = {(int32_t)fullscale, (int32_t)fullscale, (int32_t)fullscale};
-  return gpn_rulebook_level_counts(voxel_coords4, T2, counts + kV, P_ub > 0 ? P_ub : 1, grid_shape, 1, counts + kCoarse, o.sub, o.sub_bytes,
-                                   stream_);
+  return proposal_tail(pt_xyz_p, proposal_indices, proposal_offsets, counts, jitter, fullscale, max_scale, T2, P_ub, o.mean, o.scale,
+                       o.shift, o.scaled, o.rmin, o.rmax, o.vf, o.seg64, o.vc3, o.vseg, o.rv_nvox, o.rv_nout, o.rv_vbase, o.rv_kbase,
+                       o.rv_obase, o.sub, o.sub_bytes, voxel_coords4, pc_voxel_id, point_order, voxel_point_start, stream);
 }
 
 static int voxel_mean_impl(const float* feats, const int64_t* point_indices, const int32_t* point_order,
@@ -878,4 +891,319 @@ extern "C" int gpn_proposals_revoxelize(const float* scaled, const int32_t* prop
   GPN_CHECK_WS(w);
   return revoxelize(scaled, proposal_offsets, counts, T2, P_ub, fullscale, voxel_coords3, voxel_seg, pc_voxel_id, point_order,
                     voxel_point_start, a[0], a[1], a[2], a[3], a[4], (hipStream_t)stream_);
+}
+
+// ---- MP: proposals from caller-supplied masks (include/gpn.h section MP) -----------------------------------------------------------
+// The front of the proposal stage when the parts are GIVEN (a 2-D segmenter's masks lifted to the points) instead of found by
+// clustering: ragged byte masks over the caller's rows -> bit sets over the network's points (gpn_mask_pack: one ballot per word)
+// -> the ordered proposal tables (gpn_proposals_from_masks), then the tail above, unchanged.  No sort and no atomics in the fill:
+// the slot of a member is (first slot of its mask) + (members in the mask's earlier words) + (members below it in its word), so the
+// 64 lanes of a word write consecutive slots.  The union of the kept masks (valid_mask / valid_indices / the numbering behind
+// sorted_indices) takes the same pattern over OR-ed words.  A point may sit in any number of masks: no member_slot here.
+namespace {
+
+enum { kBadLabel = 5, kOverflow = 7 };  // counts[] slots of this entry point next to kQ .. kCoarse
+
+__device__ __forceinline__ uint64_t mp_lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+
+// word w of mask k with the bits at and beyond the scene's m points cleared (w < words of the scene)
+__device__ __forceinline__ uint64_t mp_word(const uint64_t* __restrict__ bits, int64_t k, int64_t w, int64_t W, int64_t m) {
+  uint64_t v = bits[k * W + w];
+  const int64_t rem = m - w * 64;
+  if (rem < 64) v &= (1ull << rem) - 1ull;
+  return v;
+}
+__device__ __forceinline__ int64_t mp_words(int64_t m, int64_t W) {
+  const int64_t words = (m + 63) >> 6;
+  return words < W ? words : W;
+}
+
+__global__ __launch_bounds__(kThreads) void mask_pack_kernel(const uint8_t* __restrict__ masks, const int64_t* __restrict__ mask_base,
+                                                             const int32_t* __restrict__ mask_scene,
+                                                             const int64_t* __restrict__ scene_offsets,
+                                                             const int64_t* __restrict__ sample_rows, int64_t K, int64_t W,
+                                                             uint64_t* __restrict__ bits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kThreads / 64);
+  for (int64_t t = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); t < K * W; t += waves) {  // (whole waves)
+    const int64_t k = t / W, w = t - k * W;
+    const int32_t s = mask_scene[k];
+    const int64_t o = scene_offsets[s], m = scene_offsets[s + 1] - o;
+    const int64_t j = w * 64 + lane;
+    bool on = false;
+    if (j < m) on = masks[mask_base[k] + (sample_rows ? sample_rows[o + j] : j)] != 0;
+    const uint64_t word = __builtin_amdgcn_ballot_w64(on);
+    if (lane == 0) bits[t] = word;
+  }
+}
+
+// one wave per mask: members in the mask's earlier words (exclusive prefix popcount), its size, whether it is kept
+__global__ __launch_bounds__(kThreads) void mp_size_kernel(const uint64_t* __restrict__ bits, const int32_t* __restrict__ mask_scene,
+                                                           const int64_t* __restrict__ mask_label,
+                                                           const int64_t* __restrict__ scene_offsets, int64_t K, int64_t W, int min_points,
+                                                           int n_classes, int32_t* __restrict__ wpre, int32_t* __restrict__ size,
+                                                           int32_t* __restrict__ keep, int32_t* __restrict__ bad) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kThreads / 64);
+  for (int64_t k = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); k < K; k += waves) {
+    const int32_t s = mask_scene[k];
+    const int64_t m = scene_offsets[s + 1] - scene_offsets[s], words = mp_words(m, W);
+    int carry = 0;
+    for (int64_t w0 = 0; w0 < words; w0 += 64) {
+      const int64_t w = w0 + lane;
+      const int c = w < words ? __builtin_popcountll(mp_word(bits, k, w, W, m)) : 0;
+      int incl = c;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+      }
+      if (w < words) wpre[k * W + w] = carry + incl - c;
+      carry += __shfl(incl, 63, 64);
+    }
+    if (lane == 0) {
+      const int64_t lab = mask_label[k];
+      const bool known = lab >= 1 && lab < (int64_t)n_classes;
+      size[k] = carry;
+      keep[k] = (known && carry >= min_points) ? 1 : 0;
+      bad[k] = known ? 0 : 1;
+    }
+  }
+}
+
+// one workgroup: the kept masks numbered in the caller's order, their first slots, the totals; a member total above M_cap sets the
+// overflow counter and leaves P = M = 0, so that nothing behind this kernel writes a per-point row
+__global__ __launch_bounds__(1024) void mp_scan_kernel(const int32_t* __restrict__ size, const int32_t* __restrict__ keep,
+                                                       const int32_t* __restrict__ bad, int64_t K, int64_t M_cap, int32_t* __restrict__ pid,
+                                                       int64_t* __restrict__ sizes, int32_t* __restrict__ proposal_offsets,
+                                                       int64_t* __restrict__ proposal_mask, int64_t* __restrict__ seg64,
+                                                       int64_t* __restrict__ counts) {
+  __shared__ long long part[3][1024];
+  __shared__ long long carry[3];
+  const int t = threadIdx.x;
+  if (t < 3) carry[t] = 0;
+  __syncthreads();
+  for (int64_t k0 = 0; k0 < K; k0 += 1024) {
+    const int64_t k = k0 + t;
+    long long v[3] = {0, 0, 0};
+    if (k < K) v[0] = keep[k], v[1] = keep[k] ? size[k] : 0, v[2] = bad[k];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) part[q][t] = v[q];
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {  // inclusive Hillis-Steele over the chunk
+      long long add[3] = {0, 0, 0};
+      if (t >= off) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) add[q] = part[q][t - off];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < 3; ++q) part[q][t] += add[q];
+      __syncthreads();
+    }
+    if (k < K) {
+      const long long p = carry[0] + part[0][t] - v[0], first = carry[1] + part[1][t] - v[1];
+      pid[k] = (int32_t)p;
+      if (v[0] && first + v[1] <= M_cap) {
+        sizes[p] = v[1];
+        proposal_offsets[p] = (int32_t)first;
+        proposal_mask[p] = k;
+        seg64[p] = first;
+      }
+    }
+    __syncthreads();
+    if (t < 3) carry[t] += part[t][1023];
+    __syncthreads();
+  }
+  const bool over = carry[1] > M_cap;
+  const int64_t P = over ? 0 : carry[0], M = over ? 0 : carry[1];
+  if (t == 0) {
+    counts[kP] = P, counts[kM] = M, counts[kBadLabel] = carry[2], counts[kOverflow] = over ? carry[1] : 0;
+  }
+  for (int64_t p = P + t; p <= K; p += 1024) proposal_offsets[p] = (int32_t)M, seg64[p] = M;  // closing offset, empty tail segments
+}
+
+// OR of the kept masks of a scene, word by word (one thread per word: neighbouring threads read neighbouring words of a mask)
+__global__ __launch_bounds__(kThreads) void mp_union_kernel(const uint64_t* __restrict__ bits, const int32_t* __restrict__ mask_scene,
+                                                            const int32_t* __restrict__ keep, const int64_t* __restrict__ scene_offsets,
+                                                            int64_t K, int64_t S, int64_t W, uint64_t* __restrict__ uni,
+                                                            int32_t* __restrict__ ucnt) {
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= S * W) return;
+  const int64_t s = t / W, w = t - s * W;
+  const int64_t m = scene_offsets[s + 1] - scene_offsets[s];
+  uint64_t u = 0;
+  if (w < mp_words(m, W)) {
+    int64_t lo = 0, hi = K;  // first mask of scene s (mask_scene is non-decreasing)
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)mask_scene[mid] < s) lo = mid + 1; else hi = mid;
+    }
+    for (int64_t k = lo; k < K && (int64_t)mask_scene[k] == s; ++k)
+      if (keep[k]) u |= mp_word(bits, k, w, W, m);
+  }
+  uni[t] = u;
+  ucnt[t] = __builtin_popcountll(u);
+}
+
+// one wave per (scene, word): valid_mask of the word's points, the valid points listed in order
+__global__ __launch_bounds__(kThreads) void mp_valid_kernel(const uint64_t* __restrict__ uni, const int32_t* __restrict__ ucnt,
+                                                            const int32_t* __restrict__ upre, const int64_t* __restrict__ scene_offsets,
+                                                            int64_t S, int64_t W, uint8_t* __restrict__ valid_mask,
+                                                            int64_t* __restrict__ valid_indices, int64_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kThreads / 64);
+  for (int64_t t = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); t < S * W; t += waves) {
+    const int64_t s = t / W, w = t - s * W;
+    const int64_t o = scene_offsets[s], m = scene_offsets[s + 1] - o;
+    const int64_t j = w * 64 + lane;
+    const uint64_t u = uni[t];
+    if (j < m) {
+      const bool on = (u >> lane) & 1ull;
+      valid_mask[o + j] = on ? 1 : 0;
+      if (on) valid_indices[upre[t] + __builtin_popcountll(u & mp_lanes_below())] = o + j;
+    }
+    if (t == S * W - 1 && lane == 0) counts[kQ] = (int64_t)upre[t] + ucnt[t];
+  }
+}
+
+struct MaskFillOut {
+  int64_t *sorted_indices, *point_indices, *proposal_indices;
+  int32_t *batch_p, *sem_p;
+  float* xyz_p;
+};
+
+// one wave per (mask, word): the members of the word into consecutive rows of the proposal-point tables
+__global__ __launch_bounds__(kThreads) void mp_fill_kernel(const uint64_t* __restrict__ bits, const int32_t* __restrict__ mask_scene,
+                                                           const int64_t* __restrict__ mask_label, const int32_t* __restrict__ keep,
+                                                           const int32_t* __restrict__ pid, const int32_t* __restrict__ wpre,
+                                                           const int32_t* __restrict__ proposal_offsets, const uint64_t* __restrict__ uni,
+                                                           const int32_t* __restrict__ upre, const int64_t* __restrict__ scene_offsets,
+                                                           const float* __restrict__ points, int stride, int64_t K, int64_t W,
+                                                           int64_t M_cap, const int64_t* __restrict__ counts, MaskFillOut out) {
+  if (counts[kOverflow] != 0) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kThreads / 64);
+  for (int64_t t = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); t < K * W; t += waves) {
+    const int64_t k = t / W, w = t - k * W;
+    if (!keep[k]) continue;
+    const int32_t s = mask_scene[k];
+    const int64_t o = scene_offsets[s], m = scene_offsets[s + 1] - o;
+    if (w >= mp_words(m, W)) continue;
+    const uint64_t word = mp_word(bits, k, w, W, m);
+    if (!((word >> lane) & 1ull)) continue;
+    const int32_t p = pid[k];
+    const int64_t slot = (int64_t)proposal_offsets[p] + wpre[t] + __builtin_popcountll(word & mp_lanes_below());
+    if (slot >= M_cap) continue;  // (cannot happen without the overflow counter set)
+    const int64_t i = o + w * 64 + lane;
+    out.sorted_indices[slot] = (int64_t)upre[s * W + w] + __builtin_popcountll(uni[s * W + w] & mp_lanes_below());
+    out.point_indices[slot] = i;
+    out.proposal_indices[slot] = p;
+    out.batch_p[slot] = s;
+    out.sem_p[slot] = (int32_t)mask_label[k];
+    out.xyz_p[slot * 3] = points[i * stride], out.xyz_p[slot * 3 + 1] = points[i * stride + 1];
+    out.xyz_p[slot * 3 + 2] = points[i * stride + 2];
+  }
+}
+
+struct MaskWs {
+  int32_t *wpre, *size, *keep, *bad, *pid, *ucnt, *upre, *vc3, *vseg, *rv[5];
+  uint64_t* uni;
+  float *mean, *scale, *shift, *scaled, *rmin, *rmax, *vf;
+  int64_t* seg64;
+  void *prim, *sub;
+  size_t prim_bytes, sub_bytes, total;
+};
+
+MaskWs mask_carve(void* ws, size_t ws_bytes, int64_t K, int64_t S, int64_t W, int64_t M_cap) {
+  gpn::WsCarver c(ws, ws_bytes);
+  const size_t k = (size_t)(K > 0 ? K : 1), sw = (size_t)(S * W > 0 ? S * W : 1), kw = (size_t)(K * W > 0 ? K * W : 1);
+  const size_t t2 = (size_t)(M_cap > 0 ? M_cap : 1), pu = k + 1;
+  MaskWs o;
+  o.wpre = c.take<int32_t>(kw), o.size = c.take<int32_t>(k), o.keep = c.take<int32_t>(k), o.bad = c.take<int32_t>(k);
+  o.pid = c.take<int32_t>(k), o.ucnt = c.take<int32_t>(sw), o.upre = c.take<int32_t>(sw), o.uni = c.take<uint64_t>(sw);
+  o.vc3 = c.take<int32_t>(3 * t2), o.vseg = c.take<int32_t>(t2);
+  for (int q = 0; q < 5; ++q) o.rv[q] = c.take<int32_t>(pu + 1);
+  o.mean = c.take<float>(3 * pu), o.scale = c.take<float>(pu), o.shift = c.take<float>(3 * pu);
+  o.scaled = c.take<float>(3 * t2), o.rmin = c.take<float>(3 * pu), o.rmax = c.take<float>(3 * pu), o.vf = c.take<float>(3 * t2);
+  o.seg64 = c.take<int64_t>(pu);
+  o.prim_bytes = prim_bytes_for((int64_t)sw);
+  o.prim = c.take<char>(o.prim_bytes);
+  o.sub_bytes = std::max(gpn_voxelize_ws_bytes((int64_t)t2, 3), gpn_rulebook_level_counts_ws_bytes((int64_t)t2, 1));
+  o.sub = c.take<char>(o.sub_bytes);
+  o.total = c.used;
+  return o;
+}
+
+inline int wave_grid(int64_t waves) {
+  return (int)std::min<int64_t>(gpn::cdiv(waves > 0 ? waves : 1, kThreads / 64), 65536);
+}
+
+}  // namespace
+
+extern "C" int gpn_mask_pack(const uint8_t* masks, const int64_t* mask_base, const int32_t* mask_scene, const int64_t* scene_offsets,
+                             const int64_t* sample_rows, int64_t K, int64_t W, uint64_t* bits, gpn_stream_t stream_) {
+  GPN_CHECK_ARG(K >= 0 && W >= 0);
+  if (K == 0 || W == 0) return GPN_OK;
+  GPN_CHECK_ARG(masks && mask_base && mask_scene && scene_offsets && bits);
+  hipLaunchKernelGGL(mask_pack_kernel, dim3(wave_grid(K * W)), dim3(kThreads), 0, (hipStream_t)stream_, masks, mask_base, mask_scene,
+                     scene_offsets, sample_rows, K, W, bits);
+  GPN_CHECK_LAUNCH();
+  return GPN_OK;
+}
+
+extern "C" size_t gpn_proposals_from_masks_ws_bytes(int64_t K, int64_t S, int64_t W, int64_t M_cap) {
+  return mask_carve(nullptr, 0, K, S, W, M_cap).total;
+}
+
+extern "C" int gpn_proposals_from_masks(const uint64_t* bits, int64_t W, const int32_t* mask_scene, const int64_t* mask_label,
+                                        const int64_t* scene_offsets, const float* points, int point_stride, int64_t K, int64_t S,
+                                        int64_t N, int min_points, int n_classes, float fullscale, float max_scale, const float* jitter,
+                                        int64_t M_cap, int64_t* counts, uint8_t* valid_mask, int64_t* valid_indices,
+                                        int64_t* sorted_indices, int64_t* point_indices, int64_t* proposal_indices,
+                                        int32_t* batch_indices_p, float* pt_xyz_p, int32_t* sem_preds_p, int64_t* sizes,
+                                        int32_t* proposal_offsets, int64_t* proposal_mask, int32_t* voxel_coords4, int32_t* pc_voxel_id,
+                                        int32_t* point_order, int32_t* voxel_point_start, void* ws, size_t ws_bytes,
+                                        gpn_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  GPN_CHECK_ARG(K >= 0 && S >= 0 && W >= 0 && N >= 0 && M_cap >= 0 && min_points >= 1 && n_classes >= 1 && point_stride >= 3);
+  GPN_CHECK_ARG(M_cap < ((int64_t)1 << 31) && N < ((int64_t)1 << 31) && W * 64 < ((int64_t)1 << 31) + 64);
+  GPN_CHECK_ARG(fullscale >= 1.0f);
+  GPN_CHECK_ARG(counts && (N == 0 || valid_mask));
+  GPN_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * kCounts, stream));
+  if (K == 0 || S == 0 || W == 0 || M_cap == 0) {  // no mask, no point, or no room for one: M = P = 0
+    if (N > 0) GPN_CHECK_HIP(hipMemsetAsync(valid_mask, 0, (size_t)N, stream));
+    return GPN_OK;
+  }
+  GPN_CHECK_ARG(bits && mask_scene && mask_label && scene_offsets && points && jitter && valid_indices);
+  GPN_CHECK_ARG(sorted_indices && point_indices && proposal_indices && batch_indices_p && pt_xyz_p && sem_preds_p);
+  GPN_CHECK_ARG(sizes && proposal_offsets && proposal_mask && voxel_coords4 && pc_voxel_id && point_order && voxel_point_start);
+  MaskWs o = mask_carve(ws, ws_bytes, K, S, W, M_cap);
+  if (!ws || ws_bytes < o.total) {
+    gpn::set_error("gpn_proposals_from_masks: workspace too small (%zu needed, %zu given)", o.total, ws_bytes);
+    return GPN_ERR_WS;
+  }
+  hipLaunchKernelGGL(mp_size_kernel, dim3(wave_grid(K)), dim3(kThreads), 0, stream, bits, mask_scene, mask_label, scene_offsets, K, W,
+                     min_points, n_classes, o.wpre, o.size, o.keep, o.bad);
+  GPN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mp_scan_kernel, dim3(1), dim3(1024), 0, stream, o.size, o.keep, o.bad, K, M_cap, o.pid, sizes, proposal_offsets,
+                     proposal_mask, o.seg64, counts);
+  GPN_CHECK_LAUNCH();
+  // ---- the union of the kept masks: valid_mask, valid_indices, the numbering sorted_indices is reported in
+  hipLaunchKernelGGL(mp_union_kernel, dim3(grid_of(S * W)), dim3(kThreads), 0, stream, bits, mask_scene, o.keep, scene_offsets, K, S, W,
+                     o.uni, o.ucnt);
+  GPN_CHECK_LAUNCH();
+  size_t tmp = o.prim_bytes;
+  GPN_CHECK_HIP(rocprim::exclusive_scan(o.prim, tmp, o.ucnt, o.upre, 0, (size_t)(S * W), rocprim::plus<int32_t>(), stream));
+  hipLaunchKernelGGL(mp_valid_kernel, dim3(wave_grid(S * W)), dim3(kThreads), 0, stream, o.uni, o.ucnt, o.upre, scene_offsets, S, W,
+                     valid_mask, valid_indices, counts);
+  GPN_CHECK_LAUNCH();
+  // ---- the proposal-point tables
+  MaskFillOut fo{sorted_indices, point_indices, proposal_indices, batch_indices_p, sem_preds_p, pt_xyz_p};
+  hipLaunchKernelGGL(mp_fill_kernel, dim3(wave_grid(K * W)), dim3(kThreads), 0, stream, bits, mask_scene, mask_label, o.keep, o.pid,
+                     o.wpre, proposal_offsets, o.uni, o.upre, scene_offsets, points, point_stride, K, W, M_cap, counts, fo);
+  GPN_CHECK_LAUNCH();
+  return proposal_tail(pt_xyz_p, proposal_indices, proposal_offsets, counts, jitter, fullscale, max_scale, M_cap, K, o.mean, o.scale,
+                       o.shift, o.scaled, o.rmin, o.rmax, o.vf, o.seg64, o.vc3, o.vseg, o.rv[0], o.rv[1], o.rv[2], o.rv[3], o.rv[4],
+                       o.sub, o.sub_bytes, voxel_coords4, pc_voxel_id, point_order, voxel_point_start, stream);
 }

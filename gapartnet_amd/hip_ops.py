@@ -1052,6 +1052,88 @@ def proposals_build(points_xyz, offset_preds, sem_preds, instance_labels, batch_
                 point_order=order[:M], voxel_point_start=vstart[:V + 1])
 
 
+# ---------------------------------------------------------------------------------------------------- MP
+def mask_tables(scene_counts, masks_per_scene, device):
+    """the small tables sections MP's two calls share, from HOST lists (no device read): points per scene of the network batch
+    and masks per scene -> dict(mask_scene [K] i32, scene_offsets [S+1] i64, K, S, N, W = words per mask, cap = sum over the
+    masks of their scene's points: the bound of the member total)"""
+    counts = [int(c) for c in scene_counts]
+    per = [int(k) for k in masks_per_scene]
+    if len(counts) != len(per) or any(c < 0 for c in counts) or any(k < 0 for k in per):
+        raise ValueError("scene_counts and masks_per_scene are per scene and non-negative")
+    scene_of = np.repeat(np.arange(len(per), dtype=np.int32), per)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return dict(mask_scene=torch.from_numpy(scene_of).to(device), scene_offsets=torch.from_numpy(off).to(device), K=int(sum(per)),
+                S=len(counts), N=int(off[-1]), W=(max(counts + [0]) + 63) // 64, cap=int(sum(c * k for c, k in zip(counts, per))))
+
+
+def mask_pack(masks, mask_base, tables, sample_rows=None):
+    """gpn_mask_pack: ``masks`` flat u8 / bool (non-zero = member), mask k = the bytes from ``mask_base[k]`` over the rows of its
+    caller's cloud; ``sample_rows`` [N] i64 = row of every network point inside its cloud (None: the masks are on the network's
+    points).  -> bits [K, W] int64 (the u64 words' bit patterns)."""
+    dev = _dev(masks, sample_rows)
+    K, W = tables["K"], tables["W"]
+    bits = torch.empty((K, W), dtype=torch.int64, device=dev)
+    if K == 0 or W == 0:
+        return bits
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    assert masks.dtype == torch.uint8 and masks.dim() == 1 and masks.is_contiguous()
+    base = torch.as_tensor(mask_base, dtype=torch.int64).to(dev).contiguous()
+    assert base.shape == (K,)
+    rows = _c(sample_rows, torch.int64)
+    assert rows is None or rows.shape == (tables["N"],)
+    check(_C.lib().gpn_mask_pack(ptr(masks), ptr(base), ptr(tables["mask_scene"]), ptr(tables["scene_offsets"]), ptr(rows), i64(K), i64(W),
+                                 ptr(bits), _stream()), "gpn_mask_pack")
+    return bits
+
+
+def proposals_from_masks(bits, tables, mask_label, points_xyz, n_classes, min_points, fullscale, max_scale, jitter, M_cap=None,
+                         _new=None):
+    """Section MP of include/gpn.h: bit sets of caller-supplied masks -> the proposal stage's tables, the re-voxelisation included, in
+    one library call and ONE host read (the counts).  Same dict as ``proposals_build`` without ``member_slot`` (a point may sit in
+    any number of masks) and with ``proposal_mask`` [P] i64 = position of every proposal in the caller's mask list; None when no mask
+    is kept.  Raises on a mask whose label lies outside [1, n_classes) and when the members exceed ``M_cap`` (default: the bound)."""
+    dev = _dev(bits, points_xyz, mask_label)
+    K, S, W, N = tables["K"], tables["S"], tables["W"], tables["N"]
+    assert points_xyz.dtype == torch.float32 and points_xyz.stride(1) == 1 and int(points_xyz.shape[0]) == N
+    assert bits.dtype == torch.int64 and tuple(bits.shape) == (K, W) and bits.is_contiguous()
+    cap = int(tables["cap"] if M_cap is None else M_cap)
+    if K == 0 or cap == 0 or N == 0:
+        return None
+    label = _c(mask_label, torch.int64)
+    assert label.shape == (K,)
+    jit = torch.cat([jitter[0].reshape(3), jitter[1].reshape(3)]).to(device=dev, dtype=torch.float32).contiguous()
+    new = _new or (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev))
+    counts = torch.empty((8,), dtype=torch.int64, device=dev)
+    valid_mask, valid_indices = new((N,), torch.bool), new((N,), torch.int64)
+    sorted_indices, point_indices, proposal_indices = new((cap,), torch.int64), new((cap,), torch.int64), new((cap,), torch.int64)
+    batch_p, sem_p, xyz_p = new((cap,), torch.int32), new((cap,), torch.int32), new((cap, 3), torch.float32)
+    sizes, offsets, prop_mask = new((K + 1,), torch.int64), new((K + 1,), torch.int32), new((K + 1,), torch.int64)
+    coords4 = new((cap, 4), torch.int32)
+    pid, order, vstart = new((cap,), torch.int32), new((cap,), torch.int32), new((cap + 1,), torch.int32)
+    L = _C.lib()
+    ws = _ws(L.gpn_proposals_from_masks_ws_bytes(i64(K), i64(S), i64(W), i64(cap)), dev)
+    check(L.gpn_proposals_from_masks(ptr(bits), i64(W), ptr(tables["mask_scene"]), ptr(label), ptr(tables["scene_offsets"]),
+                                     ptr(points_xyz), i32(points_xyz.stride(0)), i64(K), i64(S), i64(N), i32(min_points), i32(n_classes),
+                                     f32(fullscale), f32(max_scale), ptr(jit), i64(cap), ptr(counts), ptr(valid_mask), ptr(valid_indices),
+                                     ptr(sorted_indices), ptr(point_indices), ptr(proposal_indices), ptr(batch_p), ptr(xyz_p), ptr(sem_p),
+                                     ptr(sizes), ptr(offsets), ptr(prop_mask), ptr(coords4), ptr(pid), ptr(order), ptr(vstart), ptr(ws),
+                                     szt(ws.numel()), _stream()), "gpn_proposals_from_masks")
+    Q, M, P, V, dropped, bad, coarse, overflow = counts.tolist()  # the stage's single device -> host read
+    if bad:
+        raise _C.GpnError(f"proposals_from_masks: {bad} mask(s) carry a label outside [1, {n_classes})")
+    if overflow:
+        raise _C.GpnError(f"proposals_from_masks: the masks have {overflow} members, the tables hold {cap}")
+    if M == 0:
+        return None
+    return dict(counts_host=(Q, M, P, V, dropped, coarse), Q=Q, M=M, P=P, V=V, dropped=dropped, coarse=coarse, valid_mask=valid_mask,
+                valid_indices=valid_indices[:Q], sorted_indices=sorted_indices[:M], point_indices=point_indices[:M],
+                proposal_indices=proposal_indices[:M], batch_indices=batch_p[:M], pt_xyz=xyz_p[:M], sem_preds=sem_p[:M],
+                instance_labels=None, sizes=sizes[:P], proposal_offsets=offsets[:P + 1], proposal_mask=prop_mask[:P],
+                voxel_coords=coords4[:V], pc_voxel_id=pid[:M], point_order=order[:M], voxel_point_start=vstart[:V + 1])
+
+
 def proposals_postprocess(score_preds, sizes, proposal_offsets, point_indices, proposal_indices, member_slot, score_threshold,
                           min_points, iou_threshold, rows: Optional[DevCount] = None, defer: bool = False):
     """Section PP of include/gpn.h: score filter + NMS + compaction tables of a validation step's proposals in one call and ONE

@@ -6,9 +6,12 @@ end tools/visu_utils.py:141-173 ``OBJfile2points`` / ``FindMaxDis`` / ``WorldSpa
                      ``num_points``, ball normalisation over the sampled points (csrc/cloudprep.hip; include/gpn.h section CP)
 ``PartPredictor``    ``model(pcs)`` -> score filter + NMS -> per-point maps and one box per part (the kernels of the test epoch's
                      rendering) -> every row of the caller's cloud through its nearest sampled point (gpn_cloud_nearest)
+``PartPredictor.predict_with_masks``  parts the CALLER found (point masks with a part class each, on the raw rows): NPCS, a score
+                     and a 9-DoF box per mask (``GAPartNet.forward_with_masks``; csrc/proposals.hip section MP)
 ``read_obj_points``  the reference's OBJ reader
 ``python -m gapartnet_amd.inference --ckpt X --input a.npy b.obj ... --out DIR [--num_points N] [--inference_dtype bf16]
-        [--panels] [--no_flip]``
+        [--panels] [--no_flip] [--masks a.npz b.npz ...]``   (``--masks``: parallel to ``--input``, each file ``masks`` [K, N] and
+        ``labels`` [K]; the output gains the ``mask_*`` arrays and the panels draw the masks' boxes)
 
 CUDA tensors run on the HIP library; CPU tensors take the same graph in torch ops (FPS as a plain loop) - for tests and tiny
 inputs, never chosen for a CUDA tensor.
@@ -195,6 +198,34 @@ class PartPrediction:
         return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items()}
 
 
+@dataclass
+class MaskPrediction:
+    """one cloud of ``PartPredictor.predict_with_masks``: per mask of the caller, in the caller's order (K of them)"""
+    status: int                     # CLOUD_OK / CLOUD_EMPTY / CLOUD_DEGENERATE; a cloud that is not OK has every mask dropped
+    cloud_scale: torch.Tensor       # [4] f64: (r, cx, cy, cz) of the ball normalisation
+    sem: torch.Tensor               # [N] i64: the network's own part class of every row, -1 on invalid rows (as ``predict``)
+    kept: torch.Tensor              # [K] bool: the mask had at least ``min_points`` SAMPLED members
+    n_points: torch.Tensor          # [K] i64: sampled members of a kept mask, 0 for a dropped one
+    label: torch.Tensor             # [K] i64: the caller's part class
+    score: torch.Tensor             # [K] f32: sigmoid of the score head at the mask's class; NaN where dropped
+    valid: torch.Tensor             # [K] bool: a box was fitted (kept, at least 5 points, the fit found a pose)
+    scale: torch.Tensor             # [K] f64: the similarity NPCS - 0.5 -> the caller's frame (these four); NaN where not valid
+    rotation: torch.Tensor          # [K, 3, 3] f64
+    translation: torch.Tensor       # [K, 3] f64
+    transform: torch.Tensor         # [K, 4, 4] f64
+    bbox: torch.Tensor              # [K, 8, 3] f64 in the caller's frame; NaN where not valid
+    bbox_normalised: torch.Tensor   # [K, 8, 3] f64 in the network's (ball) frame
+    member_offsets: torch.Tensor    # [K + 1] i64: CSR over the masks of ...
+    member_rows: torch.Tensor       # [M] i64: ... the sampled member rows (rows of the caller's cloud, ascending sample order)
+    member_npcs: torch.Tensor       # [M, 3] f32: the NPCS of every member under ITS mask's class
+    sample_rows: torch.Tensor       # [m] i64
+    sampled_points: torch.Tensor    # [m, C] f32, normalised frame
+    sampled_sem: torch.Tensor       # [m] i64
+
+    def to_numpy(self) -> dict:
+        return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items()}
+
+
 def scene_maps_torch(valid_indices, sorted_indices, proposal_offsets, npcs_valid_mask, npcs_preds, n_rows):
     """gpn_scene_maps in torch ops (include/gpn.h section VS): a row written by several proposal points keeps the highest"""
     dev = sorted_indices.device
@@ -237,6 +268,9 @@ def _scene_predictions(kept, scene_offsets, picks, max_iters):
 
 
 Picks = Union[None, torch.Tensor, Callable[[List[int]], torch.Tensor]]
+# what the command line writes per mask (``mask_<field>`` in the cloud's .npz)
+MASK_FIELDS = ("kept", "n_points", "label", "score", "valid", "scale", "rotation", "translation", "transform", "bbox", "bbox_normalised",
+               "member_offsets", "member_rows", "member_npcs")
 
 
 class PartPredictor:
@@ -333,6 +367,122 @@ class PartPredictor:
         return out
 
 
+    def _rows_sem(self, prep: PreparedClouds, sem: torch.Tensor, net_off: List[int]) -> torch.Tensor:
+        """the part class of every row of the caller's clouds through its nearest sampled point (-1 on invalid rows)"""
+        dev = prep.source.device
+        nn = nearest_samples(prep)
+        first = torch.repeat_interleave(torch.tensor(net_off[:-1], dtype=torch.int64).to(dev),
+                                        torch.tensor([b - a for a, b in zip(prep.offsets[:-1], prep.offsets[1:])]).to(dev),
+                                        output_size=prep.offsets[-1])
+        g = (first + nn).clamp(min=0, max=max(net_off[-1] - 1, 0))
+        return torch.where(nn >= 0, sem[g], -1)
+
+    @torch.no_grad()
+    def predict_with_masks(self, clouds: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], labels: Sequence[torch.Tensor],
+                           picks: Picks = None, min_points: int = 6) -> List[MaskPrediction]:
+        """``masks[s]`` [K_s, N_s] bool / u8 on the RAW rows of cloud s (a row with a non-finite coordinate is never sampled, so it is
+        never a member), ``labels[s]`` [K_s] part classes.  A mask with fewer than ``min_points`` SAMPLED members is dropped (the
+        reference's ``sum > 5``, structure/gapartnet.py:635).  Every kept mask is fitted with its OWN NPCS (a point shared by two
+        masks carries two predictions); a box needs at least 5 points and a valid fit (the reference's ``<= 4: continue``)."""
+        model = self.model
+        prep = prepare_clouds(clouds, self.num_points)
+        C = prep.source.shape[1]
+        if C < model.in_channels:
+            raise ValueError(f"the model reads {model.in_channels} columns per point, the clouds have {C}")
+        dev = prep.source.device
+        S = len(prep.offsets) - 1
+        if len(masks) != S or len(labels) != S:
+            raise ValueError(f"{S} clouds need {S} mask tensors and {S} label tensors")
+        masks = [torch.as_tensor(m).to(dev) for m in masks]
+        labels = [torch.as_tensor(v).to(dev).long().reshape(-1) for v in labels]
+        for s in range(S):
+            n = prep.offsets[s + 1] - prep.offsets[s]
+            if masks[s].dim() != 2 or masks[s].shape[0] != labels[s].shape[0] or (masks[s].shape[0] and masks[s].shape[1] != n):
+                raise ValueError(f"cloud {s}: masks must be [K, {n}] with one label per mask, got {tuple(masks[s].shape)} and "
+                                 f"{labels[s].shape[0]} labels")
+        counts = prep.counts.tolist()
+        net_off = [0]
+        for c in counts:
+            net_off.append(net_off[-1] + c)
+        ok = [s for s in range(S) if counts[s] > 0]
+        f64, i64, nan = torch.float64, torch.int64, float("nan")
+
+        def dropped(s, K):
+            z = lambda *shape, dtype=f64, fill=nan: torch.full(shape, fill, dtype=dtype, device=dev)  # noqa: E731
+            n = prep.offsets[s + 1] - prep.offsets[s]
+            return MaskPrediction(
+                status=int(prep.status[s]), cloud_scale=prep.scale[s], sem=z(n, dtype=i64, fill=-1), kept=z(K, dtype=torch.bool, fill=False),
+                n_points=z(K, dtype=i64, fill=0), label=labels[s], score=z(K, dtype=torch.float32), valid=z(K, dtype=torch.bool, fill=False),
+                scale=z(K), rotation=z(K, 3, 3), translation=z(K, 3), transform=z(K, 4, 4), bbox=z(K, 8, 3), bbox_normalised=z(K, 8, 3),
+                member_offsets=z(K + 1, dtype=i64, fill=0), member_rows=z(0, dtype=i64, fill=0), member_npcs=z(0, 3, dtype=torch.float32),
+                sample_rows=z(0, dtype=i64, fill=0), sampled_points=z(0, C, dtype=torch.float32), sampled_sem=z(0, dtype=i64, fill=0))
+
+        out = [dropped(s, int(masks[s].shape[0])) for s in range(S)]
+        if not ok:
+            return out
+        pcs = [PointCloud(pc_id=str(s), points=prep.points[net_off[s]:net_off[s + 1], :model.in_channels].contiguous(), obj_cat=0)
+               for s in ok]
+        _, sem_seg, props, _ = model.forward_with_masks(pcs, [masks[s] for s in ok], [labels[s] for s in ok], min_points=min_points,
+                                                        sample_rows=prep.sample_rows)
+        sem = sem_seg.sem_preds.long()
+        sem_all = self._rows_sem(prep, sem, net_off)
+        # per mask of the batch (the OK clouds' masks, concatenated): scattered from the kept ones
+        gstart = [0]
+        for s in ok:
+            gstart.append(gstart[-1] + int(masks[s].shape[0]))
+        Kt = gstart[-1]
+        full = lambda *shape, dtype=f64, fill=nan: torch.full((Kt,) + shape, fill, dtype=dtype, device=dev)  # noqa: E731
+        kept, n_points, score, valid = full(dtype=torch.bool, fill=False), full(dtype=i64, fill=0), full(dtype=torch.float32), \
+            full(dtype=torch.bool, fill=False)
+        pose = dict(scale=full(), rotation=full(3, 3), translation=full(3), transform=full(4, 4), bbox=full(8, 3))
+        sizes_host = [0] * Kt
+        if props is not None:
+            pm = props.proposal_mask
+            po = props.proposal_offsets.long()
+            sizes = po[1:] - po[:-1]
+            n_points[pm] = sizes
+            sizes_host = n_points.tolist()  # the call's one read behind the model's: member CSR of every cloud, the fits' draws
+            kept_sizes = [n for n in sizes_host if n > 0]
+            if callable(picks):
+                picks = picks(kept_sizes)
+            elif picks is None:
+                from .misc.pose_fitting_batched import draw_picks
+                picks = draw_picks(kept_sizes, self.max_iters)
+            fit = estimate_pose_from_npcs_batched(props.pt_xyz, props.npcs_preds - 0.5, po, picks=picks, max_iters=self.max_iters)
+            box = (sizes >= 5) & fit["valid"]
+            kept[pm], score[pm], valid[pm] = True, props.score_preds, box
+            for f in pose:
+                shape = (-1,) + (1,) * (fit[f].dim() - 1)
+                pose[f][pm] = torch.where(box.reshape(shape), fit[f], torch.full_like(fit[f], nan))
+            member_rows = prep.sample_rows.index_select(0, props.point_indices)
+        cum = np.concatenate([[0], np.cumsum(sizes_host)]).astype(np.int64)
+        cum_dev = torch.from_numpy(cum).to(dev)
+        for k, s in enumerate(ok):
+            a, b = prep.offsets[s], prep.offsets[s + 1]
+            na, nb = net_off[s], net_off[s + 1]
+            g0, g1 = gstart[k], gstart[k + 1]
+            o = out[s]
+            o.sem = sem_all[a:b]
+            o.sample_rows, o.sampled_points, o.sampled_sem = prep.sample_rows[na:nb], prep.points[na:nb], sem[na:nb]
+            o.kept, o.n_points, o.score, o.valid = kept[g0:g1], n_points[g0:g1], score[g0:g1], valid[g0:g1]
+            sc = prep.scale[s].to(dev)
+            r, c = sc[0], sc[1:]
+            # caller's frame = normalised * r + c: the similarity's linear part and translation scale by r, the centre is added
+            o.scale, o.rotation = pose["scale"][g0:g1] * r, pose["rotation"][g0:g1]
+            o.translation = pose["translation"][g0:g1] * r + c
+            T = pose["transform"][g0:g1].clone()
+            T[:, :3, :3] = T[:, :3, :3] * r
+            T[:, :3, 3] = o.translation
+            o.transform = T
+            o.bbox_normalised = pose["bbox"][g0:g1]
+            o.bbox = o.bbox_normalised * r + c
+            o.member_offsets = cum_dev[g0:g1 + 1] - int(cum[g0])
+            if props is not None:
+                o.member_rows = member_rows[int(cum[g0]):int(cum[g1])]
+                o.member_npcs = props.npcs_preds[int(cum[g0]):int(cum[g1])]
+        return out
+
+
 # ---------------------------------------------------------------------------------------------------- files and the command line
 def read_obj_points(path: str) -> np.ndarray:
     """the reference's OBJfile2points (tools/visu_utils.py:141-155): every line ``v x y z r g b`` up to the first ``vt`` line
@@ -372,9 +522,19 @@ def _read_cloud(path: str, flip: bool) -> np.ndarray:
     raise ValueError(f"{path}: inputs are .npy arrays [N, C >= 3] or .obj files with `v x y z r g b` lines")
 
 
-def _write_panels(preds: Sequence[PartPrediction], names: Sequence[str], out_dir: str):
-    """the prediction tiles of the test epoch's panel (misc/visu.render_panels) over the sampled points of every OK cloud"""
+def _write_panels(preds: Sequence[PartPrediction], names: Sequence[str], out_dir: str, mask_preds=None):
+    """the prediction tiles of the test epoch's panel (misc/visu.render_panels) over the sampled points of every OK cloud; with
+    ``mask_preds`` (predict_with_masks) the box tiles draw the caller's masks' boxes instead of the clustered parts'"""
     from .misc import visu
+    if mask_preds is not None:
+        import copy
+        shown = []
+        for p, mp in zip(preds, mask_preds):
+            p = copy.copy(p)
+            if p.status == CLOUD_OK:
+                p.bbox_normalised, p.bbox = mp.bbox_normalised[mp.valid], mp.bbox[mp.valid]
+            shown.append(p)
+        preds = shown
     rows = [(n, p) for n, p in zip(names, preds) if p.status == CLOUD_OK]
     if not rows:
         return []
@@ -408,6 +568,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--inference_dtype", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--panels", action="store_true")
     ap.add_argument("--no_flip", action="store_true", help="keep the y and z signs of .obj inputs")
+    ap.add_argument("--masks", nargs="+", default=None,
+                    help="one .npz per input, in order: `masks` [K, N] on the input's rows and `labels` [K] part classes")
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
     args = ap.parse_args(argv)
     device = torch.device(args.device)
@@ -415,6 +577,17 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--panels renders on the GPU (misc/visu.render_panels): it cannot be combined with --device cpu")
     model = load_model(args.ckpt, device, args.inference_dtype)
     clouds = [torch.from_numpy(_read_cloud(p, not args.no_flip)).to(device) for p in args.input]
+    given = None
+    if args.masks is not None:
+        if len(args.masks) != len(args.input):
+            ap.error(f"--masks takes one file per input ({len(args.input)}), got {len(args.masks)}")
+        given = []
+        for path, cloud in zip(args.masks, clouds):
+            z = np.load(path)
+            m, lab = np.asarray(z["masks"]) != 0, np.asarray(z["labels"]).astype(np.int64).reshape(-1)
+            if m.ndim != 2 or m.shape != (lab.shape[0], cloud.shape[0]):
+                ap.error(f"{path}: `masks` must be [K, {cloud.shape[0]}] with `labels` [K], got {m.shape} and {lab.shape}")
+            given.append((torch.from_numpy(m).to(device), torch.from_numpy(lab).to(device)))
     names = [os.path.splitext(os.path.basename(p))[0] for p in args.input]
     os.makedirs(args.out, exist_ok=True)
     # (one batch per column count: a batch shares its C)
@@ -424,12 +597,26 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ids = [i for i, c in enumerate(clouds) if c.shape[1] == C]
         for i, p in zip(ids, predictor.predict([clouds[i] for i in ids])):
             preds[i] = p
-    for name, p in zip(names, preds):
-        np.savez(os.path.join(args.out, name + ".npz"), **p.to_numpy())
-        print(f"{name}: {STATUS_NAMES.get(p.status, p.status)}, {p.sem.shape[0]} rows, {p.proposal_scores.shape[0]} parts, "
-              f"{p.bbox.shape[0]} boxes")
+    mask_preds: Optional[List[Optional[MaskPrediction]]] = None
+    if given is not None:
+        mask_preds = [None] * len(clouds)
+        for C in sorted({int(c.shape[1]) for c in clouds}):
+            ids = [i for i, c in enumerate(clouds) if c.shape[1] == C]
+            got = predictor.predict_with_masks([clouds[i] for i in ids], [given[i][0] for i in ids], [given[i][1] for i in ids])
+            for i, p in zip(ids, got):
+                mask_preds[i] = p
+    for k, (name, p) in enumerate(zip(names, preds)):
+        arrays = p.to_numpy()
+        line = (f"{name}: {STATUS_NAMES.get(p.status, p.status)}, {p.sem.shape[0]} rows, {p.proposal_scores.shape[0]} parts, "
+                f"{p.bbox.shape[0]} boxes")
+        if mask_preds is not None:
+            mp = mask_preds[k]
+            arrays.update({"mask_" + f: v for f, v in mp.to_numpy().items() if f in MASK_FIELDS})
+            line += f"; {mp.kept.shape[0]} masks, {int(mp.kept.sum())} kept, {int(mp.valid.sum())} boxes"
+        np.savez(os.path.join(args.out, name + ".npz"), **arrays)
+        print(line)
     if args.panels:
-        _write_panels(preds, names, args.out)
+        _write_panels(preds, names, args.out, mask_preds)
     return 0
 
 

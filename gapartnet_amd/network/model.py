@@ -750,6 +750,199 @@ class GAPartNet(LightningModule):
         finally:
             self._want_npcs_preds, self.sync_free_proposals, self._prop_gate = saved
 
+    # ------------------------------------------------------------------------------------------ parts from caller-supplied masks
+    @staticmethod
+    def _scene_counts(data_batch: PointCloudBatch) -> List[int]:
+        counts = data_batch.scene_counts
+        if counts is None:
+            counts = torch.bincount(data_batch.batch_indices.long(), minlength=data_batch.batch_size).tolist()
+        return [int(c) for c in counts]
+
+    @staticmethod
+    def _mask_lists(counts, masks, labels, sample_rows, device):
+        """the caller's per-cloud masks / labels -> (list of [K_s, n_s] u8 tensors, masks per scene, labels [K] i64)"""
+        S = len(counts)
+        if len(masks) != S or len(labels) != S:
+            raise ValueError(f"{S} clouds need {S} mask tensors and {S} label tensors (got {len(masks)} / {len(labels)})")
+        per, flat, labs = [], [], []
+        for s in range(S):
+            m = masks[s]
+            lab = torch.as_tensor(labels[s] if labels[s] is not None else [], dtype=torch.int64).reshape(-1).to(device)
+            if m is None or lab.shape[0] == 0 and torch.as_tensor(m).numel() == 0:
+                m = torch.zeros((0, counts[s]), dtype=torch.uint8, device=device)
+            m = torch.as_tensor(m).to(device)
+            if m.dtype == torch.bool:
+                m = m.view(torch.uint8) if m.is_contiguous() else m.to(torch.uint8)
+            if m.dtype != torch.uint8:
+                m = (m != 0).to(torch.uint8)
+            if m.dim() != 2 or m.shape[0] != lab.shape[0]:
+                raise ValueError(f"cloud {s}: masks must be [K, n] with one label per mask (got {tuple(m.shape)} and {lab.shape[0]} labels)")
+            if sample_rows is None and m.shape[0] and m.shape[1] != counts[s]:
+                raise ValueError(f"cloud {s}: masks cover {m.shape[1]} points, the cloud has {counts[s]}")
+            per.append(int(m.shape[0]))
+            flat.append(m.contiguous())
+            labs.append(lab)
+        return flat, per, torch.cat(labs) if labs else torch.zeros(0, dtype=torch.int64, device=device)
+
+    def _mask_jitter(self, device):
+        """(jitter, undo): the re-voxelisation's two uniform 3-vectors - injected ones, or drawn as segmented_voxelize draws them;
+        ``undo()`` puts the generator back when no mask is kept (the draws happen only when a proposal survives)"""
+        if self.revoxelize_jitter is not None:
+            return self.revoxelize_jitter, lambda: None
+        gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()] \
+            if device.type == "cuda" else torch.default_generator
+        state = gen.get_state()
+        jitter = (torch.rand(3, dtype=torch.float32, device=device), torch.rand(3, dtype=torch.float32, device=device))
+        return jitter, lambda: gen.set_state(state)
+
+    def proposals_from_masks_torch(self, pt_xyz, pt_features, counts, flat, per, mask_label, min_points, sample_rows, jitter):
+        """the mask stage in torch ops (CPU tensors, operator backends without ``proposals_from_masks``; what the kernels are tested
+        against): ``nonzero`` per kept mask, then segmented_voxelize.  -> (voxel_tensor, pc_voxel_id, Instances) or three None."""
+        dev = pt_xyz.device
+        N = pt_xyz.shape[0]
+        lab_host = mask_label.tolist()
+        bad = sum(1 for v in lab_host if not 1 <= v < self.num_part_classes)
+        if bad:
+            raise RuntimeError(f"proposals_from_masks: {bad} mask(s) carry a label outside [1, {self.num_part_classes})")
+        rows, which, first, k = [], [], 0, 0
+        for s, c in enumerate(counts):
+            for j in range(per[s]):
+                m = flat[s][j]
+                if sample_rows is not None:
+                    m = m[sample_rows[first:first + c]]
+                r = torch.nonzero(m != 0).squeeze(1)
+                if r.shape[0] >= min_points:
+                    rows.append(r + first)
+                    which.append((k, s))
+                k += 1
+            first += c
+        if not rows:
+            return None, None, None
+        sizes = torch.tensor([r.shape[0] for r in rows], dtype=torch.int64, device=dev)
+        point_indices = torch.cat(rows)
+        proposal_indices = torch.repeat_interleave(torch.arange(len(rows), device=dev), sizes)
+        proposal_mask = torch.tensor([w[0] for w in which], dtype=torch.int64, device=dev)
+        valid_mask = torch.zeros((N,), dtype=torch.bool, device=dev)
+        valid_mask[point_indices] = True
+        valid_indices = torch.nonzero(valid_mask).squeeze(1)
+        sorted_indices = (valid_mask.long().cumsum(0) - 1)[point_indices]
+        proposal_offsets = offsets_from_counts(sizes)
+        xyz_p = pt_xyz[point_indices]
+        voxel_features, voxel_coords, pc_voxel_id, extras = segmented_voxelize(
+            xyz_p, pt_features[point_indices], proposal_offsets, proposal_indices, sizes, self.score_fullscale, self.score_scale,
+            jitter=jitter, with_extras=True)
+        if extras["dropped"] != 0:
+            raise RuntimeError("re-voxelisation dropped points: a mask left its score_fullscale^3 grid")
+        voxel_tensor = spconv.SparseConvTensor(voxel_features, voxel_coords.int(), spatial_shape=[self.score_fullscale] * 3,
+                                               batch_size=len(rows))
+        voxel_tensor.point_csr = extras["csr"]
+        proposals = Instances(valid_mask=valid_mask, valid_indices=valid_indices, sorted_indices=sorted_indices,
+                              point_indices=point_indices, pt_xyz=xyz_p,
+                              batch_indices=torch.tensor([w[1] for w in which], dtype=torch.int32, device=dev)[proposal_indices],
+                              proposal_offsets=proposal_offsets, proposal_indices=proposal_indices, num_points_per_proposal=sizes,
+                              sem_preds=mask_label[proposal_mask][proposal_indices].int(), proposal_mask=proposal_mask)
+        return voxel_tensor, pc_voxel_id, proposals
+
+    def _proposals_from_masks(self, pt_xyz, pt_features, counts, flat, per, mask_label, min_points, sample_rows):
+        ops = backend.raw()
+        jitter, undo = self._mask_jitter(pt_xyz.device)
+        if not (self.use_fused_proposals and pt_xyz.is_cuda and hasattr(ops, "proposals_from_masks")):
+            out = self.proposals_from_masks_torch(pt_xyz, pt_features, counts, flat, per, mask_label, min_points, sample_rows, jitter)
+            if out[2] is None:
+                undo()
+            return out
+        # masks -> bit sets on the network's points -> the proposal tables, on the device (csrc/proposals.hip section MP): ONE host read
+        tables = ops.mask_tables(counts, per, pt_xyz.device)
+        base, first = [], 0
+        for m in flat:
+            base += [first + j * int(m.shape[1]) for j in range(int(m.shape[0]))]
+            first += int(m.numel())
+        bits = ops.mask_pack(torch.cat([m.reshape(-1) for m in flat]) if first else torch.zeros(0, dtype=torch.uint8, device=pt_xyz.device),
+                             base, tables, sample_rows)
+        built = ops.proposals_from_masks(bits, tables, mask_label, pt_xyz, self.num_part_classes, min_points,
+                                         float(self.score_fullscale), float(self.score_scale), jitter)
+        if built is None:
+            undo()
+            return None, None, None
+        if built["dropped"] != 0:
+            raise RuntimeError("re-voxelisation dropped points: a mask left its score_fullscale^3 grid")
+        voxel_features = ops.proposals_voxel_mean(pt_features, built["point_indices"], built["point_order"], built["voxel_point_start"],
+                                                  built["V"])
+        voxel_tensor = spconv.SparseConvTensor(voxel_features, built["voxel_coords"], spatial_shape=[self.score_fullscale] * 3,
+                                               batch_size=built["P"])
+        voxel_tensor.level_counts = [built["coarse"]]
+        voxel_tensor.point_csr = (built["point_order"], built["voxel_point_start"])
+        proposals = Instances(valid_mask=built["valid_mask"], valid_indices=built["valid_indices"],
+                              sorted_indices=built["sorted_indices"], point_indices=built["point_indices"], pt_xyz=built["pt_xyz"],
+                              batch_indices=built["batch_indices"], proposal_offsets=built["proposal_offsets"],
+                              proposal_indices=built["proposal_indices"], num_points_per_proposal=built["sizes"],
+                              sem_preds=built["sem_preds"], proposal_mask=built["proposal_mask"])
+        return voxel_tensor, built["pc_voxel_id"], proposals
+
+    @torch.no_grad()
+    def forward_with_masks(self, point_clouds: Union[Sequence[PointCloud], PointCloudBatch], masks, labels,
+                           min_points: Optional[int] = None, sample_rows: Optional[torch.Tensor] = None):
+        """NPCS, a score and the tables of a 9-DoF fit for parts the CALLER found (a 2-D segmenter's masks lifted to the points) -
+        the reference's ``perception_model.forward_with_masks(pcs, masks, labels)`` (structure/utils.py:195-322; the contract is
+        chosen from the call sites) -> (pc_ids, Segmentation, Instances or None, proposal_sem_labels [P] i64).
+        ``masks``: per cloud one [K_s, m_s] bool / u8 tensor on the cloud's own points (non-zero = member; None or K_s = 0: no
+        mask); ``labels``: per cloud [K_s] part classes in [1, num_part_classes).  ``sample_rows`` [sum m_s] i64 (PartPredictor):
+        the masks are on the rows of the caller's RAW clouds and network point i is row sample_rows[i] of its cloud.
+        Runs as ``forward`` does (no labels read, epoch gates passed, ``inference_dtype`` honoured, the training steps' proposal
+        plan untouched); the backbone and both point heads run, so ``Segmentation.sem_preds`` is the network's own.  The mask
+        stage replaces the clustering: proposals = the masks with at least ``min_points`` (default: min_num_points_per_proposal)
+        members, in the caller's order, members ascending; a point may sit in many.  ``proposals.proposal_mask`` [P] = position in
+        the concatenated mask list, ``sem_preds`` = the MASK's label at every proposal point, ``score_preds[p]`` =
+        sigmoid(score_logits[p, label_p - 1]), ``npcs_preds`` [M,3] = the triple of the mask's class, ``npcs_valid_mask`` all true.
+        No score filter and no NMS: the caller chose the parts."""
+        if not isinstance(point_clouds, PointCloudBatch):
+            point_clouds = [self._without_labels(pc) for pc in point_clouds]
+        data_batch = self._collate(point_clouds)
+        pt_xyz = data_batch.points[:, :3]
+        pc_feature = self.forward_backbone(pc_batch=data_batch)
+        sem_logits = self.forward_sem_seg(pc_feature)
+        self.forward_offset(pc_feature)
+        sem_seg = Segmentation(batch_size=data_batch.batch_size, sem_preds=torch.argmax(sem_logits, dim=-1))
+        counts = self._scene_counts(data_batch)
+        flat, per, mask_label = self._mask_lists(counts, masks, labels, sample_rows, pt_xyz.device)
+        min_points = int(self.min_num_points_per_proposal if min_points is None else min_points)
+        voxel_tensor, pc_voxel_id, proposals = self._proposals_from_masks(pt_xyz, pc_feature, counts, flat, per, mask_label,
+                                                                         max(min_points, 1), sample_rows)
+        if proposals is None:
+            return data_batch.pc_ids, sem_seg, None, mask_label[:0]
+        pair = self.forward_proposal_unets(voxel_tensor)
+        score_feats, npcs_feats = pair if pair is not None else (None, None)
+        score_logits = self.forward_proposal_score(voxel_tensor, pc_voxel_id, proposals, score_feats)
+        proposal_sem_labels = mask_label.index_select(0, proposals.proposal_mask)
+        proposals.score_preds = score_logits.gather(1, proposal_sem_labels[:, None] - 1).squeeze(1).sigmoid()
+        npcs_logits = self.forward_proposal_npcs(voxel_tensor, pc_voxel_id, npcs_feats, None)
+        cls = proposals.sem_preds.long()
+        per_class = npcs_logits.reshape(npcs_logits.shape[0], npcs_logits.shape[1] // 3, 3)
+        proposals.npcs_preds = per_class.gather(1, (cls - 1)[:, None, None].expand(-1, 1, 3)).squeeze(1)
+        proposals.npcs_valid_mask = torch.ones((cls.shape[0],), dtype=torch.bool, device=cls.device)
+        return data_batch.pc_ids, sem_seg, proposals, proposal_sem_labels
+
+    @torch.no_grad()
+    def estimate_pose_from_mask(self, point_clouds: Sequence[PointCloud], min_points: Optional[int] = None):
+        """the reference's ``perception_model.estimate_pose_from_mask(pcs)`` (structure/utils.py:195-260): ``forward_with_masks`` with
+        the masks the clouds carry - ``pc_masks`` [K, N] (or a list of [N] masks), ``mask_labels`` [K], ``mask_ids`` (any K
+        identifiers, optional) -> (pc_ids, Instances or None).  ``Instances.mask_ids`` lists the caller's identifier of every
+        proposal (its position in the cloud's masks where the cloud gives none)."""
+        masks, labels, ids = [], [], []
+        for pc in point_clouds:
+            m = pc.pc_masks
+            if isinstance(m, (list, tuple)):
+                m = torch.stack([torch.as_tensor(x) for x in m]) if len(m) else None
+            masks.append(m)
+            labels.append(pc.mask_labels if m is not None else None)
+            K = 0 if m is None else int(torch.as_tensor(m).shape[0])
+            own = pc.mask_ids
+            ids += list(own.tolist() if hasattr(own, "tolist") else own) if own is not None else list(range(K))
+        pc_ids, _, proposals, _ = self.forward_with_masks(point_clouds, masks, labels, min_points=min_points)
+        if proposals is not None:
+            proposals.mask_ids = [ids[k] for k in proposals.proposal_mask.tolist()]
+        return pc_ids, proposals
+
     # ------------------------------------------------------------------------------------------ Lightning hooks
     def training_step(self, point_clouds, batch_idx: int):
         return self._training_or_validation_step(point_clouds, batch_idx, "train")[3]

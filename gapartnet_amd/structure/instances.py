@@ -37,6 +37,10 @@ class Instances:
     # not a reference field: {"M", "P", "V"} -> hip_ops.DevCount when the proposal stage ran without a host read - every tensor
     # above then has the rows of a bound and only the first *count rows are defined (training steps only)
     dev_counts: Optional[dict] = None
+    # not reference fields: proposals made from caller-supplied masks (GAPartNet.forward_with_masks) - position of every proposal in
+    # the caller's concatenated mask list, and the caller's identifiers of those masks (estimate_pose_from_mask)
+    proposal_mask: Optional[torch.Tensor] = None
+    mask_ids: Optional[list] = None
 
 
 @dataclass

@@ -61,13 +61,20 @@ class PointCloud:
     voxel_coords: Optional[torch.Tensor] = None
     voxel_coords_range: Optional[List[int]] = None
     pc_voxel_id: Optional[torch.Tensor] = None
+    # parts found by the caller (GAPartNet.estimate_pose_from_mask): [K, N] point masks (or a list of K masks, stacked by to_tensor),
+    # their part classes [K] and any K identifiers.  collate does not read them.
+    pc_masks: Optional[Union[torch.Tensor, np.ndarray, list]] = None
+    mask_labels: Optional[Union[torch.Tensor, np.ndarray]] = None
+    mask_ids: Optional[Union[torch.Tensor, np.ndarray, list]] = None
 
     def to_dict(self) -> Dict[str, Any]:
         return {f.name: getattr(self, f.name) for f in fields(self)}
 
     def to_tensor(self) -> "PointCloud":
-        return PointCloud(**{k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v)
-                             for k, v in self.to_dict().items()})
+        d = self.to_dict()
+        if isinstance(d["pc_masks"], (list, tuple)):  # a list of K masks -> [K, N]
+            d["pc_masks"] = torch.stack([torch.as_tensor(m) for m in d["pc_masks"]]) if len(d["pc_masks"]) else None
+        return PointCloud(**{k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in d.items()})
 
     def to(self, device) -> "PointCloud":
         return PointCloud(**{k: (v.to(device) if isinstance(v, torch.Tensor) else v)

@@ -644,6 +644,40 @@ int gpn_proposals_voxel_mean_bwd(const float* dout, const int32_t* member_slot, 
                                  const int32_t* voxel_point_start, int64_t N, int C, float* dfeats, gpn_stream_t stream);
 
 /* ================================================================================================
+ * MP - proposals from caller-supplied masks: the front of the proposal stage when the parts are GIVEN (point masks with a part
+ * class each: a 2-D segmenter's masks lifted to the points) instead of found by clustering.  Serves the reference's deployment
+ * calls estimate_pose_from_mask / forward_with_masks (structure/utils.py:195-322); the contract is chosen from those call sites
+ * (INTEGRATION.md).  Inference only: no member_slot, no backward, no gpn_proposals_postprocess behind it.
+ * gpn_mask_pack: masks on the caller's rows -> bit sets on the network's points.  masks u8 (non-zero = member), mask k is the run
+ * of bytes starting at mask_base[k] (i64) over the rows of the caller's cloud mask_scene[k] (i32, non-decreasing; a scene may own
+ * no mask); scene_offsets [S+1] i64 = the scenes' rows in the network batch; sample_rows [n_net] i64 = row of every network point
+ * inside its caller's cloud, or NULL = identity.  bits [K, W] u64, W = ceil(max m_s / 64): bit (j & 63) of word (j >> 6) of mask
+ * k is set iff network point scene_offsets[s] + j is a member; bits at and beyond m_s are zero.  One wave per word (ballot); only
+ * the K m sampled bytes are read.
+ * gpn_proposals_from_masks: the bit sets -> the tables of section PR.  A mask is kept iff it has >= min_points members and
+ * 1 <= mask_label[k] < n_classes.  Proposals = the kept masks in the caller's order, members ascending; a point may sit in any
+ * number of them.  valid_mask [N] u8 = member of at least one kept mask, valid_indices the valid points, sorted_indices the
+ * numbering among them (row = valid_indices[sorted_indices]).  Per proposal point [M_cap]: sorted_indices, point_indices,
+ * proposal_indices i64, batch_indices_p i32, pt_xyz_p [.,3] f32, sem_preds_p i32 = the mask's label, pc_voxel_id, point_order i32
+ * (+ voxel_point_start [M_cap+1]); per proposal [K+1]: sizes i64, proposal_offsets i32, proposal_mask i64 = k; voxel_coords4
+ * [M_cap,4].  Then the tail of gpn_proposals_build (frame, re-voxelisation into fullscale^3 grids - sort-free for fullscale <= 30,
+ * the sorting voxeliser above - coarse-level rows).  counts [8] i64 (device): {Q, M, P, V, dropped, masks with a label outside
+ * [1, n_classes), coarse rows, overflow}.  A member total above M_cap sets counts[7] to that total, leaves M = P = 0 and writes
+ * no per-point row.  K = 0 (or no scene, W = 0, M_cap = 0): every count 0, valid_mask cleared.  Nothing is read back.
+ * ================================================================================================ */
+int gpn_mask_pack(const uint8_t* masks, const int64_t* mask_base, const int32_t* mask_scene, const int64_t* scene_offsets,
+                  const int64_t* sample_rows, int64_t K, int64_t W, uint64_t* bits, gpn_stream_t stream);
+size_t gpn_proposals_from_masks_ws_bytes(int64_t K, int64_t S, int64_t W, int64_t M_cap);
+int gpn_proposals_from_masks(const uint64_t* bits, int64_t W, const int32_t* mask_scene, const int64_t* mask_label,
+                             const int64_t* scene_offsets, const float* points, int point_stride, int64_t K, int64_t S, int64_t N,
+                             int min_points, int n_classes, float fullscale, float max_scale, const float* jitter, int64_t M_cap,
+                             int64_t* counts, uint8_t* valid_mask, int64_t* valid_indices, int64_t* sorted_indices,
+                             int64_t* point_indices, int64_t* proposal_indices, int32_t* batch_indices_p, float* pt_xyz_p,
+                             int32_t* sem_preds_p, int64_t* sizes, int32_t* proposal_offsets, int64_t* proposal_mask,
+                             int32_t* voxel_coords4, int32_t* pc_voxel_id, int32_t* point_order, int32_t* voxel_point_start, void* ws,
+                             size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * BP - the preparation of one batch for a sparse U-Net in ONE call (round 5): gpn_voxelize_scenes, its one host read, and the
  * rulebook pyramid of the backbone - per level the SubM k = 3 tables (+ tile order from tile_order_min_rows rows), the stride-2
  * map to the next level and its transpose (+ tile order), and, for the levels in the bit mask ident_levels, the k = 1 identity
