@@ -1,0 +1,777 @@
+"""Articulated URDF assets -> training views (the reference's dataset/render_tools/render.py without SAPIEN).
+
+What the training set takes from the reference's renderer is a z-depth map, a per-pixel link id turned into semantic and instance
+labels, an NPCS map computed from the articulated part boxes, an RGB image and the metadata files the converter reads
+(gapartnet_amd/dataset/convert_rendered.py).  Here the asset is parsed on the host (URDF through xml.etree, OBJ / MTL by hand),
+joints and a camera are drawn in the reference's order, the part boxes are articulated exactly as the reference does it, and a batch
+of views is rasterised by the kernels of include/gpn.h section RD: one kernel batch and one device-to-host copy per batch.
+
+    asset = load_asset(path)                       # geometry + joints + target links
+    rng = numpy.random.RandomState(0)
+    req = RenderRequest(0, sample_qpos(asset, rng), sample_camera(DEFAULT_CAMERA_RANGE, rng))
+    view, = render_views([asset], [req], 800, 800) # RenderedView: rgb, depth, sem, ins, npcs, bbox_pose_dict, ...
+    write_view(out, "StorageFurniture_45780_0_0", view)
+
+On a CPU device ``render_views`` runs ``render_tables_numpy``, a vectorised numpy formulation of the same contracts (the baseline of
+tools/render_bench.py, and what a machine without a GPU can check).  RGB is flat-shaded base colour: textures, point lights,
+shadows, ray tracing and ``replace_texture`` are out of scope; depth, labels, NPCS, boxes and metadata are the contract.
+
+DECISIONS: the camera frame of ``camera_frame``; polygons are fan-triangulated; triangles with a vertex nearer
+than 0.1 are dropped whole; pixel (x, y) samples the ray through u = x, v = y.
+"""
+import argparse
+import json
+import math
+import os
+import pickle
+import sys
+import time
+import xml.etree.ElementTree as ET
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from ..misc import info
+
+# the part classes of the annotation files, in the order that defines category_id: the project's list without "others"; the
+# annotation files spell the last class "hinge_handle" (the training side calls it revolute_handle)
+GAPART_NAMES = list(info.TARGET_PARTS[1:-1]) + ["hinge_handle"]
+BACKGROUND_RGB = (216, 206, 189)
+DEFAULT_GREY = 0.8
+LIGHT_WORLD = (0.0, 1.0, -1.0)  # the reference's directional light
+FOV_DEG = 35.0
+# the range used for a category that --camera_ranges does not list (ours: in front of the asset, slightly above)
+DEFAULT_CAMERA_RANGE = dict(theta_min=35.0, theta_max=75.0, phi_min=135.0, phi_max=225.0, distance_min=3.6, distance_max=4.4)
+COUNTER_NAMES = ("index", "near", "guard", "zero_area", "offscreen")
+CAM_DOUBLES, FRAME_DOUBLES = 20, 13
+NEAR, GUARD = 0.1, 16384 * 256
+
+
+# ---------------------------------------------------------------------------------------------------- parsing
+def _floats(text, default):
+    return [float(x) for x in text.split()] if text is not None else list(default)
+
+
+def rpy_matrix(rpy):
+    """URDF fixed-axis roll-pitch-yaw: Rz(yaw) Ry(pitch) Rx(roll)"""
+    r, p, y = (float(a) for a in rpy)
+    cr, sr, cp, sp, cy, sy = math.cos(r), math.sin(r), math.cos(p), math.sin(p), math.cos(y), math.sin(y)
+    Rx = np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]], dtype=np.float64)
+    Ry = np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]], dtype=np.float64)
+    Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]], dtype=np.float64)
+    return Rz @ Ry @ Rx
+
+
+def _pose(xyz, rpy):
+    m = np.eye(4)
+    m[:3, :3] = rpy_matrix(rpy)
+    m[:3, 3] = xyz
+    return m
+
+
+def axangle_matrix(axis, angle):
+    """Rodrigues rotation about a unit axis"""
+    x, y, z = (float(a) for a in axis)
+    c, s = math.cos(angle), math.sin(angle)
+    C = 1.0 - c
+    xs, ys, zs = x * s, y * s, z * s
+    xC, yC, zC = x * C, y * C, z * C
+    xyC, yzC, zxC = x * yC, y * zC, z * xC
+    return np.array([[x * xC + c, xyC - zs, zxC + ys], [xyC + zs, y * yC + c, yzC - xs], [zxC - ys, yzC + xs, z * zC + c]])
+
+
+def read_joints(urdf_path):
+    """the joints dictionary exactly as the reference's read_utils.read_joints_from_urdf_file builds it (document order)"""
+    root = ET.parse(urdf_path).getroot()
+    joints = {}
+    for joint in root.iter('joint'):
+        jt = joint.attrib['type']
+        child = [c.attrib['link'] for c in joint.iter('child')][-1]
+        parent = [c.attrib['link'] for c in joint.iter('parent')][-1]
+        xyz, rpy = [0, 0, 0], [0, 0, 0]
+        for origin in joint.iter('origin'):
+            xyz = [float(x) for x in origin.attrib['xyz'].split()] if 'xyz' in origin.attrib else [0, 0, 0]
+            rpy = [float(x) for x in origin.attrib['rpy'].split()] if 'rpy' in origin.attrib else [0, 0, 0]
+        axis = limit = None
+        if jt in ('prismatic', 'revolute', 'continuous'):
+            for a in joint.iter('axis'):
+                axis = [float(x) for x in a.attrib['xyz'].split()]
+        if jt in ('prismatic', 'revolute'):
+            for lim in joint.iter('limit'):
+                limit = [float(lim.attrib['lower']), float(lim.attrib['upper'])]
+        joints[joint.attrib['name']] = dict(type=jt, parent=parent, child=child, xyz=xyz, rpy=rpy, axis=axis, limit=limit)
+    return joints
+
+
+def read_mtl(path):
+    """material name -> Kd (map_Kd and everything else is ignored)"""
+    out, cur = {}, None
+    if not os.path.exists(path):
+        return out
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == 'newmtl':
+                cur = ' '.join(tok[1:])
+            elif tok[0] == 'Kd' and cur is not None and len(tok) >= 4:
+                out[cur] = [float(tok[1]), float(tok[2]), float(tok[3])]
+    return out
+
+
+def read_obj(path):
+    """-> (verts [n,3] f32, tris [m,3] i32, colours [m,3] f32).  `v` and `f` lines only; a/b/c forms and negative (relative)
+    indices; polygons are fan-triangulated around their first vertex (DECISION); the colour of a face is the Kd of the active
+    usemtl in the mtllib files, 0.8 grey when there is none."""
+    verts, tris, cols = [], [], []
+    mats, kd = {}, [DEFAULT_GREY] * 3
+    base = os.path.dirname(path)
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == 'v':
+                verts.append([float(tok[1]), float(tok[2]), float(tok[3])])
+            elif tok[0] == 'mtllib':
+                for name in tok[1:]:
+                    mats.update(read_mtl(os.path.join(base, name)))
+            elif tok[0] == 'usemtl':
+                kd = mats.get(' '.join(tok[1:]), [DEFAULT_GREY] * 3)
+            elif tok[0] == 'f':
+                idx = []
+                for t in tok[1:]:
+                    i = int(t.split('/')[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if not 0 <= i < len(verts):
+                        raise ValueError(f'{path}: face index {t} outside the {len(verts)} vertices read so far')
+                    idx.append(i)
+                for j in range(1, len(idx) - 1):
+                    tris.append([idx[0], idx[j], idx[j + 1]])
+                    cols.append(kd)
+    return (np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(tris, np.int32).reshape(-1, 3),
+            np.asarray(cols, np.float32).reshape(-1, 3))
+
+
+@dataclass
+class Asset:
+    path: str
+    base_link_name: str
+    joints: Dict[str, dict]            # the reference's joints dictionary
+    links: List[str]                   # URDF order
+    visual_link: np.ndarray            # [n_visuals] i32
+    visual_origin: np.ndarray          # [n_visuals,4,4] f64
+    verts: np.ndarray                  # [Nv,3] f32 as parsed
+    tris: np.ndarray                   # [Nt,3] i32
+    tri_visual: np.ndarray             # [Nt] i32
+    tri_link: np.ndarray               # [Nt] i32
+    tri_color: np.ndarray              # [Nt,3] f32
+    targets: Dict[str, dict]           # annotation order: link name -> {category_id, bbox [8,3] f32}
+    link_cat: np.ndarray = field(default=None)   # [L] i32, -1 for a link that is no target
+    link_rank: np.ndarray = field(default=None)  # [L] i32, position in the annotation file, -1 likewise
+
+
+def read_targets(anno_path):
+    """annotation entries that are GAParts of a known class, in file order -> link name -> {category_id, bbox [8,3] f32}"""
+    with open(anno_path) as fh:
+        entries = json.load(fh)
+    known = {name: i for i, name in enumerate(GAPART_NAMES)}
+    return {e['link_name']: dict(category_id=known[e['category']], bbox=np.asarray(e['bbox'], np.float32).reshape(-1, 3))
+            for e in entries if e['is_gapart'] and e['category'] in known}
+
+
+def load_asset(path, urdf="mobility_annotation_gapartnet.urdf", anno="link_annotation_gapartnet.json", base_link_name="base"):
+    urdf_path = os.path.join(path, urdf)
+    root = ET.parse(urdf_path).getroot()
+    joints = read_joints(urdf_path)
+    links, v_link, v_origin = [], [], []
+    verts, tris, tri_visual, tri_link, tri_color = [], [], [], [], []
+    nv = 0
+    for li, link in enumerate(root.findall('link')):
+        links.append(link.attrib['name'])
+        for visual in link.findall('visual'):
+            origin = visual.find('origin')
+            xyz = _floats(origin.attrib.get('xyz') if origin is not None else None, (0, 0, 0))
+            rpy = _floats(origin.attrib.get('rpy') if origin is not None else None, (0, 0, 0))
+            mesh = visual.find('geometry').find('mesh')
+            if mesh is None:
+                continue
+            v, t, c = read_obj(os.path.join(path, mesh.attrib['filename']))
+            scale = _floats(mesh.attrib.get('scale'), (1, 1, 1))
+            o = _pose(xyz, rpy)
+            o[:3, :3] = o[:3, :3] * np.asarray(scale, np.float64)[None, :]
+            vi = len(v_link)
+            v_link.append(li)
+            v_origin.append(o)
+            verts.append(v)
+            tris.append(t + nv)
+            tri_visual.append(np.full(len(t), vi, np.int32))
+            tri_link.append(np.full(len(t), li, np.int32))
+            tri_color.append(c)
+            nv += len(v)
+
+    def cat(parts, shape, dt):
+        return np.concatenate(parts).astype(dt) if parts else np.zeros(shape, dt)
+
+    targets = read_targets(os.path.join(path, anno)) if anno else {}
+    asset = Asset(path=path, base_link_name=base_link_name, joints=joints, links=links,
+                  visual_link=np.asarray(v_link, np.int32), visual_origin=np.asarray(v_origin, np.float64).reshape(-1, 4, 4),
+                  verts=cat(verts, (0, 3), np.float32), tris=cat(tris, (0, 3), np.int32), tri_visual=cat(tri_visual, (0,), np.int32),
+                  tri_link=cat(tri_link, (0,), np.int32), tri_color=cat(tri_color, (0, 3), np.float32), targets=targets)
+    asset.link_cat = np.full(len(links), -1, np.int32)
+    asset.link_rank = np.full(len(links), -1, np.int32)
+    for rank, (name, d) in enumerate(targets.items()):
+        if name in links:
+            asset.link_cat[links.index(name)] = d['category_id']
+            asset.link_rank[links.index(name)] = rank
+    return asset
+
+
+# ---------------------------------------------------------------------------------------------------- sampling
+CONTINUOUS_RANGE = (-10000.0, 10000.0)
+
+
+def sample_qpos(asset, rng):
+    """one draw per movable joint from a numpy.random.RandomState, joints in URDF order (the reference's order): uniform inside the
+    limit for prismatic and revolute joints, uniform over CONTINUOUS_RANGE for continuous ones; fixed joints get 0.0 without a draw"""
+    qpos = {}
+    for name, joint in asset.joints.items():
+        kind = joint['type']
+        if kind == 'fixed':
+            qpos[name] = 0.0
+            continue
+        if kind not in ('prismatic', 'revolute', 'continuous'):
+            raise ValueError(f"joint {name}: no sampling rule for a joint of type {kind!r}")
+        lo, hi = CONTINUOUS_RANGE if kind == 'continuous' else joint['limit']
+        qpos[name] = rng.uniform(lo, hi)
+    return qpos
+
+
+def sample_camera(camera_range, rng):
+    """polar angle theta, azimuth phi (degrees) and distance, drawn in this order (the reference's); -> position [3] looking at 0"""
+    theta, phi, distance = (rng.uniform(camera_range[k + '_min'], camera_range[k + '_max']) for k in ('theta', 'phi', 'distance'))
+    rad = math.pi / 180
+    sin_t = math.sin(rad * theta)
+    return np.array([sin_t * math.cos(rad * phi), sin_t * math.sin(rad * phi), math.cos(rad * theta)]) * distance
+
+
+# ---------------------------------------------------------------------------------------------------- kinematics
+def _joint_motion(j, q):
+    m = np.eye(4)
+    if j['type'] in ('revolute', 'continuous'):
+        a = np.asarray(j['axis'], np.float64)
+        m[:3, :3] = axangle_matrix(a / np.linalg.norm(a), q)
+    elif j['type'] == 'prismatic':
+        a = np.asarray(j['axis'], np.float64)
+        m[:3, 3] = a / np.linalg.norm(a) * q
+    return m
+
+
+def link_poses(asset, qpos):
+    """forward kinematics in float64: link name -> 4 x 4 world pose (root links at the identity).  Places the meshes."""
+    child_joint = {j['child']: name for name, j in asset.joints.items()}
+    poses = {}
+
+    def pose(link):
+        if link not in poses:
+            if link in child_joint:
+                name = child_joint[link]
+                j = asset.joints[name]
+                poses[link] = pose(j['parent']) @ _pose(j['xyz'], j['rpy']) @ _joint_motion(j, float(qpos.get(name, 0.0)))
+            else:
+                poses[link] = np.eye(4)
+        return poses[link]
+
+    for link in asset.links:
+        pose(link)
+    return poses
+
+
+def joint_states(asset, qpos):
+    """origin and axis of every joint in the world at the current qpos (parent link pose * joint origin)"""
+    poses = link_poses(asset, qpos)
+    states = {}
+    for name, j in asset.joints.items():
+        m = poses[j['parent']] @ _pose(j['xyz'], j['rpy'])
+        axis = m[:3, :3] @ np.asarray(j['axis'], np.float64) if j['axis'] is not None else np.array([1.0, 0.0, 0.0])
+        states[name] = dict(origin=m[:3, 3].copy(), axis=axis)
+    return states
+
+
+def _joints_from_root(asset, link):
+    """the joints between a link and the root of its tree, root side first, and the root's name"""
+    above = {j['child']: name for name, j in asset.joints.items()}
+    path = []
+    while link in above:
+        path.append(above[link])
+        link = asset.joints[above[link]]['parent']
+    return path[::-1], link
+
+
+def _carry(kind, origin, axis, q):
+    """the world motion (4 x 4) a joint at `origin` with unit `axis` gives to what it carries, at joint value q"""
+    m = np.eye(4)
+    if kind == 'prismatic':
+        m[:3, 3] = axis * q
+    else:  # revolute, continuous: turn about the line through origin
+        m[:3, :3] = axangle_matrix(axis, q)
+        m[:3, 3] = origin - m[:3, :3] @ origin
+    return m
+
+
+def part_boxes(asset, qpos):
+    """the annotated part boxes at a joint configuration, by the reference's rule (query_part_pose_from_joint_qpos): a box is
+    annotated in the world at rest; every movable joint between the link and the base moves it, the one nearest the base first and
+    the joint AT the base never, each about its origin and axis in the world at the CURRENT configuration.  The motions are
+    composed into one 4 x 4 per link.  A box no joint moves stays the float32 annotation, as in the reference.
+    -> link name -> {category_id, bbox [8,3]} in annotation order."""
+    where = joint_states(asset, qpos)
+    out = {}
+    for link, target in asset.targets.items():
+        path, root = _joints_from_root(asset, link)
+        if root != asset.base_link_name:
+            raise ValueError(f"{link}: its joints lead to {root!r}, not to the base link {asset.base_link_name!r}")
+        total, moved = np.eye(4), False
+        for name in path[1:]:
+            kind = asset.joints[name]['type']
+            if kind != 'fixed':
+                axis = where[name]['axis']
+                total = _carry(kind, where[name]['origin'], axis / np.linalg.norm(axis), qpos[name]) @ total
+                moved = True
+        corners = target['bbox']
+        if moved:
+            corners = corners.astype(np.float64) @ total[:3, :3].T + total[:3, 3]
+        out[link] = dict(category_id=target['category_id'], bbox=corners)
+    return out
+
+
+# corner k of a box in its own frame, in units of half an extent: the annotation's corner order
+CORNER_SIGNS = np.array([[-1, 1, 1], [1, 1, 1], [1, -1, 1], [-1, -1, 1], [-1, 1, -1], [1, 1, -1], [1, -1, -1], [-1, -1, -1]], np.float64)
+
+
+def fit_rotation(src, dst):
+    """Kabsch fit between two centred point sets [n,3]: U @ Vt of the SVD of the cross-covariance src^T dst; when that is a
+    reflection its first column is negated (the reference's repair, kept so that the stored R matches)"""
+    a, b = src - src.mean(axis=0), dst - dst.mean(axis=0)
+    u, _, vt = np.linalg.svd(a.T @ b)
+    q = u @ vt
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def npcs_frames(boxes):
+    """the normalised part frame of every box, as get_NPCS_map_from_oriented_bbox defines it: T = the corners' mean, S = the three
+    extents (|c1 - c0|, |c1 - c2|, |c0 - c4|), scaler = |S|, R = the fitted rotation between the axis-aligned box of those extents
+    and the centred corners, both divided by scaler.  boxes: link name -> {bbox} or -> bbox.  -> link name -> {R, T, S, scaler}"""
+    frames = {}
+    for name, box in boxes.items():
+        corners = box['bbox'] if isinstance(box, dict) else box
+        centre = corners.mean(axis=0)
+        extents = np.array([np.linalg.norm(corners[i] - corners[j]) for i, j in ((1, 0), (1, 2), (0, 4))])
+        scaler = np.linalg.norm(extents)
+        upright = CORNER_SIGNS * (extents / 2) / scaler
+        frames[name] = {'R': fit_rotation(upright, (corners - centre) / scaler), 'T': centre, 'S': extents, 'scaler': scaler}
+    return frames
+
+
+def camera_frame(cam_pos, H, W):
+    """-> (K [3,3], world2camera_rotation [3,3], camera2world_translation [3]) as set_all_scene + get_camera_pos_mat produce them:
+    forward = -p/|p|, left = z x forward (normalised), up = forward x left; the rotation's columns are (-left, -up, forward) - a
+    camera point is (world - t) @ R, x to the right, y down, z forward - and K has fov 35 degrees on both axes, cx = W/2, cy = H/2."""
+    p = np.asarray(cam_pos, np.float64)
+    forward = -p / np.linalg.norm(p)
+    left = np.cross([0, 0, 1], forward)
+    left = left / np.linalg.norm(left)
+    up = np.cross(forward, left)
+    R = np.stack([-left, -up, forward], axis=1)
+    t = math.tan(math.radians(FOV_DEG) / 2.0)
+    K = np.array([[W / 2.0 / t, 0.0, W / 2.0], [0.0, H / 2.0 / t, H / 2.0], [0.0, 0.0, 1.0]])
+    return K, R, p.copy()
+
+
+# ---------------------------------------------------------------------------------------------------- batches
+@dataclass
+class RenderRequest:
+    asset: int                 # index into the assets list
+    joint_qpos: Dict[str, float]
+    camera_pos: np.ndarray
+
+
+@dataclass
+class RenderedView:
+    rgb: np.ndarray            # [H,W,3] u8
+    depth: np.ndarray          # [H,W] f32
+    sem: np.ndarray            # [H,W] i32
+    ins: np.ndarray            # [H,W] i32
+    npcs: np.ndarray           # [H,W,3] f32
+    tri: np.ndarray            # [H,W] i32 (row of the batch's triangle table, -1 where empty)
+    link_area: np.ndarray      # [L] i32
+    link_inst: np.ndarray      # [L] i32
+    counters: Dict[str, int]   # dropped triangles by rule
+    bbox_pose_dict: dict       # visible target links in annotation order
+    joint_qpos: Dict[str, float]
+    camera_pos: np.ndarray
+    camera_intrinsic: np.ndarray
+    world2camera_rotation: np.ndarray
+    camera2world_translation: np.ndarray
+
+
+def geometry_tables(assets):
+    """the per-asset-set tables of section RD (uploaded once)"""
+    v0 = t0 = 0
+    verts, tris, table = [], [], []
+    for a in assets:
+        verts.append(a.verts)
+        tris.append(a.tris + v0)
+        table.append([t0, len(a.tris), len(a.visual_link), len(a.links)])
+        v0 += len(a.verts)
+        t0 += len(a.tris)
+    z = np.zeros
+    return dict(verts=np.concatenate(verts).astype(np.float32) if assets else z((0, 3), np.float32),
+                tris=np.concatenate(tris).astype(np.int32) if assets else z((0, 3), np.int32),
+                tri_visual=np.concatenate([a.tri_visual for a in assets]).astype(np.int32) if assets else z((0,), np.int32),
+                tri_link=np.concatenate([a.tri_link for a in assets]).astype(np.int32) if assets else z((0,), np.int32),
+                tri_color=np.concatenate([a.tri_color for a in assets]).astype(np.float32) if assets else z((0, 3), np.float32),
+                assets=np.asarray(table, np.int32).reshape(-1, 4))
+
+
+def view_tables(assets, requests, H, W):
+    """the per-view tables of section RD, plus what the files need -> (tables, per-view extras)"""
+    V = len(requests)
+    used = [assets[r.asset] for r in requests]
+    M = max([len(a.visual_link) for a in used] + [1])
+    L = max([len(a.links) for a in used] + [1])
+    t = dict(view_asset=np.asarray([r.asset for r in requests], np.int32).reshape(V), cam=np.zeros((V, CAM_DOUBLES)),
+             vis_mat=np.zeros((V, M, 12)), link_cat=np.full((V, L), -1, np.int32), link_rank=np.full((V, L), -1, np.int32),
+             link_frame=np.zeros((V, L, FRAME_DOUBLES)), Nt_max=max([len(a.tris) for a in used] + [0]), H=int(H), W=int(W))
+    t['link_frame'][:, :, 3] = 1.0
+    light = np.asarray(LIGHT_WORLD, np.float64) / np.linalg.norm(LIGHT_WORLD)
+    extras = []
+    for v, (r, a) in enumerate(zip(requests, used)):
+        K, R, tr = camera_frame(r.camera_pos, H, W)
+        t['cam'][v, :4] = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        t['cam'][v, 4:13] = R.reshape(-1)
+        t['cam'][v, 13:16] = tr
+        t['cam'][v, 16:19] = light @ R
+        w2c = np.eye(4)
+        w2c[:3, :3] = R.T
+        w2c[:3, 3] = -(R.T @ tr)
+        poses = link_poses(a, r.joint_qpos)
+        for i, (li, o) in enumerate(zip(a.visual_link, a.visual_origin)):
+            t['vis_mat'][v, i] = (w2c @ poses[a.links[li]] @ o)[:3, :4].reshape(-1)
+        boxes = part_boxes(a, r.joint_qpos)
+        frames = npcs_frames(boxes)
+        nl = len(a.links)
+        t['link_cat'][v, :nl] = a.link_cat
+        t['link_rank'][v, :nl] = a.link_rank
+        for name, f in frames.items():
+            if name in a.links:
+                li = a.links.index(name)
+                t['link_frame'][v, li, :3] = f['T']
+                t['link_frame'][v, li, 3] = f['scaler']
+                t['link_frame'][v, li, 4:] = np.asarray(f['R'], np.float64).reshape(-1)
+        extras.append(dict(K=K, R=R, t=tr, boxes=boxes, frames=frames))
+    return t, extras
+
+
+# ---------------------------------------------------------------------------------------------------- numpy path
+def _edge(ax, ay, bx, by, px, py):
+    return (bx - ax) * (py - ay) - (by - ay) * (px - ax)
+
+
+def render_tables_numpy(g, t):
+    """section RD on the host, vectorised over triangles (setup) and over each triangle's pixel box (raster) and over pixels
+    (annotate): the same operation order in float64, the same integers.  -> dict of the kernels' outputs."""
+    V, H, W = len(t['view_asset']), t['H'], t['W']
+    L = t['link_cat'].shape[1]
+    M = t['vis_mat'].shape[1]
+    out = dict(depth=np.zeros((V, H, W), np.float32), tri=np.full((V, H, W), -1, np.int32), sem=np.zeros((V, H, W), np.int32),
+               ins=np.zeros((V, H, W), np.int32), npcs=np.zeros((V, H, W, 3), np.float32), rgb=np.zeros((V, H, W, 3), np.uint8),
+               link_area=np.zeros((V, L), np.int32), link_inst=np.full((V, L), -1, np.int32),
+               counters=np.zeros((V, len(COUNTER_NAMES)), np.int32))
+    A, Nt, Nv = len(g['assets']), len(g['tris']), len(g['verts'])
+    ys, xs = np.mgrid[0:H, 0:W]
+    for v in range(V):
+        a = int(t['view_asset'][v])
+        first, count, nvis, nlinks = (int(x) for x in g['assets'][a]) if 0 <= a < A else (0, 0, 0, 0)
+        if first < 0 or count < 0 or first > Nt or count > Nt - first:
+            count = 0
+        count = min(count, t['Nt_max'])
+        cam = t['cam'][v]
+        fx, fy, cx, cy = cam[:4]
+        best = np.zeros((H, W), np.float64)
+        win = np.full((H, W), -1, np.int64)
+        shade = np.zeros(count, np.float64)
+        if count:
+            sl = slice(first, first + count)
+            tr, vis = g['tris'][sl].astype(np.int64), g['tri_visual'][sl].astype(np.int64)
+            bad = (vis < 0) | (vis >= M) | (vis >= nvis) | (tr < 0).any(1) | (tr >= Nv).any(1)
+            out['counters'][v, 0] = int(bad.sum())
+            live = ~bad
+            tr, vis = np.where(bad[:, None], 0, tr), np.where(bad, 0, vis)
+            m = t['vis_mat'][v][vis].reshape(-1, 1, 3, 4)                      # [n,1,3,4]
+            p = g['verts'][tr].astype(np.float64)                              # [n,3 vertices,3]
+            x, y, z = p[..., 0:1], p[..., 1:2], p[..., 2:3]
+            P = ((m[..., 0] * x + m[..., 1] * y) + m[..., 2] * z) + m[..., 3]  # [n,3 vertices,3 rows]
+            with np.errstate(all='ignore'):
+                near = live & ~(P[..., 2] >= NEAR).all(1)
+                out['counters'][v, 1] = int(near.sum())
+                live &= ~near
+                su = np.rint(((fx * P[..., 0]) / P[..., 2] + cx) * 256.0)
+                sv = np.rint(((fy * P[..., 1]) / P[..., 2] + cy) * 256.0)
+                guard = live & ~((np.abs(su) <= GUARD) & (np.abs(sv) <= GUARD)).all(1)
+            out['counters'][v, 2] = int(guard.sum())
+            live &= ~guard
+            X = np.where(live[:, None], su, 0).astype(np.int64)
+            Y = np.where(live[:, None], sv, 0).astype(np.int64)
+            area2 = _edge(X[:, 0], Y[:, 0], X[:, 1], Y[:, 1], X[:, 2], Y[:, 2])
+            zero = live & (area2 == 0)
+            out['counters'][v, 3] = int(zero.sum())
+            live &= ~zero
+            with np.errstate(all='ignore'):
+                iz = 1.0 / P[..., 2]
+            flip = area2 < 0
+            X[flip] = X[flip][:, [0, 2, 1]]
+            Y[flip] = Y[flip][:, [0, 2, 1]]
+            iz[flip] = iz[flip][:, [0, 2, 1]]
+            e1, e2 = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
+            nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+            ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+            nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+            with np.errstate(all='ignore'):
+                nn = np.sqrt((nx * nx + ny * ny) + nz * nz)
+                d = (nx * cam[16] + ny * cam[17]) + nz * cam[18]
+                shade = np.where(nn > 0.0, 0.5 + 0.5 * (np.abs(d) / nn), 0.5)
+            x0 = np.maximum((X.min(1) + 255) >> 8, 0)
+            x1 = np.minimum(X.max(1) >> 8, W - 1)
+            y0 = np.maximum((Y.min(1) + 255) >> 8, 0)
+            y1 = np.minimum(Y.max(1) >> 8, H - 1)
+            off = live & ((x0 > x1) | (y0 > y1))
+            out['counters'][v, 4] = int(off.sum())
+            live &= ~off
+            for k in np.nonzero(live)[0]:
+                bx0, bx1, by0, by1 = int(x0[k]), int(x1[k]), int(y0[k]), int(y1[k])
+                px = xs[by0:by1 + 1, bx0:bx1 + 1].astype(np.int64) * 256
+                py = ys[by0:by1 + 1, bx0:bx1 + 1].astype(np.int64) * 256
+                ok = np.ones(px.shape, bool)
+                E = []
+                for i, j in ((1, 2), (2, 0), (0, 1)):
+                    e = _edge(X[k, i], Y[k, i], X[k, j], Y[k, j], px, py)
+                    dx, dy = X[k, j] - X[k, i], Y[k, j] - Y[k, i]
+                    ok &= (e > 0) if not (dy < 0 or (dy == 0 and dx > 0)) else (e >= 0)
+                    E.append(e)
+                if not ok.any():
+                    continue
+                a2 = ((E[0] + E[1]) + E[2]).astype(np.float64)
+                l0, l1, l2 = E[0].astype(np.float64) / a2, E[1].astype(np.float64) / a2, E[2].astype(np.float64) / a2
+                invz = (l0 * iz[k, 0] + l1 * iz[k, 1]) + l2 * iz[k, 2]
+                b = best[by0:by1 + 1, bx0:bx1 + 1]
+                w = win[by0:by1 + 1, bx0:bx1 + 1]
+                take = ok & (invz > b)   # ascending k: a tie keeps the lower triangle
+                b[take] = invz[take]
+                w[take] = k
+        hit = win >= 0
+        with np.errstate(all='ignore'):
+            out['depth'][v] = np.where(hit, (1.0 / best), 0.0).astype(np.float32)
+        out['tri'][v] = np.where(hit, first + win, -1)
+        # annotate
+        link = np.full((H, W), -1, np.int64)
+        if hit.any():
+            tl = g['tri_link'][first + win[hit]].astype(np.int64)
+            link[hit] = np.where((tl >= 0) & (tl < min(nlinks, L)), tl, -1)
+        out['link_area'][v] = np.bincount(link[link >= 0], minlength=L)[:L]
+        cnt = 0
+        cat, rank = t['link_cat'][v], t['link_rank'][v]
+        by_rank = {int(rank[l]): l for l in range(L) if 0 <= rank[l] < L and cat[l] >= 0}
+        for r in sorted(by_rank):
+            if out['link_area'][v, by_rank[r]] > 0:
+                out['link_inst'][v, by_rank[r]] = cnt
+                cnt += 1
+        lk = np.maximum(link, 0)
+        target = (link >= 0) & (cat[lk] >= 0) & (out['link_inst'][v][lk] >= 0)
+        sem = np.where(target, cat[lk], -1)
+        ins = np.where(target, out['link_inst'][v][lk], -1)
+        empty = np.abs(out['depth'][v]) < np.float32(1e-6)
+        sem[empty] = -2
+        ins[empty] = -2
+        out['sem'][v], out['ins'][v] = sem, ins
+        z = out['depth'][v].astype(np.float64)
+        pc = [((xs.astype(np.float64) - cx) * z) / fx, ((ys.astype(np.float64) - cy) * z) / fy, z]
+        R, tt, f = cam[4:13].reshape(3, 3), cam[13:16], t['link_frame'][v][lk]
+        gq = [((((pc[0] * R[r, 0] + pc[1] * R[r, 1]) + pc[2] * R[r, 2]) + tt[r]) - f[..., r]) / f[..., 3] for r in range(3)]
+        for r in range(3):
+            q = (gq[0] * f[..., 4 + 3 * r] + gq[1] * f[..., 5 + 3 * r]) + gq[2] * f[..., 6 + 3 * r]
+            out['npcs'][v, ..., r] = np.where(ins >= 0, q, 0.0).astype(np.float32)
+        rgb = np.empty((H, W, 3), np.uint8)
+        rgb[:] = np.asarray(t.get('background', BACKGROUND_RGB), np.uint8)
+        if hit.any():
+            col = g['tri_color'][first + win[hit]].astype(np.float64) * shade[win[hit]][:, None]
+            rgb[hit] = np.clip(np.rint(col * 255.0), 0, 255).astype(np.uint8)
+        out['rgb'][v] = rgb
+    return out
+
+
+def render_tables_hip(g, t, device):
+    """section RD on the GPU: uploads, one kernel batch, ONE device-to-host copy of every result"""
+    import torch
+    from .. import hip_ops
+    dev = torch.device(device)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+
+    gd = {k: up(a) for k, a in g.items()}
+    td = {k: up(a) for k, a in t.items() if isinstance(a, np.ndarray)}
+    buf, layout = hip_ops.render_batch(gd, td, t['H'], t['W'], t['Nt_max'], t.get('background', BACKGROUND_RGB))
+    host = buf.cpu()
+    return {k: a.numpy() for k, a in hip_ops.render_fields(host, layout).items()}
+
+
+def render_views(assets, requests, H, W, device=None) -> List[RenderedView]:
+    """requests (RenderRequest: asset index, joint qpos, camera position) -> RenderedView each.  device None: cuda:0 when there
+    is one, else the numpy path; "cpu": the numpy path."""
+    if device is None:
+        import torch
+        device = 'cuda:0' if torch.cuda.is_available() else 'cpu'
+    g = geometry_tables(assets)
+    t, extras = view_tables(assets, requests, H, W)
+    if not requests:
+        return []
+    o = render_tables_numpy(g, t) if str(device).startswith('cpu') else render_tables_hip(g, t, device)
+    views = []
+    for v, (r, ex) in enumerate(zip(requests, extras)):
+        a = assets[r.asset]
+        inst = o['link_inst'][v]
+        bbox_pose = {}
+        for name in a.targets:  # annotation order = instance id order
+            if name in a.links and inst[a.links.index(name)] >= 0:
+                bbox_pose[name] = {'bbox': ex['boxes'][name]['bbox'], 'category_id': ex['boxes'][name]['category_id'],
+                                   'instance_id': int(inst[a.links.index(name)]), 'pose_RTS_param': ex['frames'][name]}
+        views.append(RenderedView(rgb=o['rgb'][v], depth=o['depth'][v], sem=o['sem'][v], ins=o['ins'][v], npcs=o['npcs'][v],
+                                  tri=o['tri'][v], link_area=o['link_area'][v][:len(a.links)], link_inst=inst[:len(a.links)],
+                                  counters={n: int(c) for n, c in zip(COUNTER_NAMES, o['counters'][v])}, bbox_pose_dict=bbox_pose,
+                                  joint_qpos=dict(r.joint_qpos), camera_pos=np.asarray(r.camera_pos, np.float64),
+                                  camera_intrinsic=ex['K'], world2camera_rotation=ex['R'], camera2world_translation=ex['t']))
+    return views
+
+
+# ---------------------------------------------------------------------------------------------------- files
+def write_view(save_path, name, view: RenderedView, meta: Optional[dict] = None):
+    """the renderer's layout (save_rgb_image, save_depth_map, save_anno_dict, save_meta).  meta: model_id, category, camera_idx,
+    render_idx for the metafile (None where unknown)."""
+    from PIL import Image
+    for sub in ('rgb', 'depth', 'segmentation', 'bbox', 'npcs', 'metafile'):
+        os.makedirs(os.path.join(save_path, sub), exist_ok=True)
+    Image.fromarray(view.rgb).save(os.path.join(save_path, 'rgb', f'{name}.png'))
+    np.savez_compressed(os.path.join(save_path, 'depth', f'{name}.npz'), depth_map=view.depth)
+    np.savez_compressed(os.path.join(save_path, 'segmentation', f'{name}.npz'), semantic_segmentation=view.sem,
+                        instance_segmentation=view.ins)
+    np.savez_compressed(os.path.join(save_path, 'npcs', f'{name}.npz'), npcs_map=view.npcs)
+    with open(os.path.join(save_path, 'bbox', f'{name}.pkl'), 'wb') as fd:
+        pickle.dump({'bbox_pose_dict': view.bbox_pose_dict}, fd)
+    meta = meta or {}
+    H, W = view.depth.shape
+    metafile = {
+        'model_id': meta.get('model_id'), 'category': meta.get('category'), 'camera_idx': meta.get('camera_idx'),
+        'render_idx': meta.get('render_idx'), 'width': W, 'height': H,
+        'joint_qpos': {k: float(q) for k, q in view.joint_qpos.items()},
+        'camera_pos': view.camera_pos.reshape(-1).tolist(),
+        'camera_intrinsic': view.camera_intrinsic.reshape(-1).tolist(),
+        'world2camera_rotation': view.world2camera_rotation.reshape(-1).tolist(),
+        'camera2world_translation': view.camera2world_translation.reshape(-1).tolist(),
+        'target_gaparts': list(GAPART_NAMES), 'use_raytracing': False, 'replace_texture': False,
+    }
+    with open(os.path.join(save_path, 'metafile', f'{name}.json'), 'w') as fd:
+        json.dump(metafile, fd)
+
+
+# ---------------------------------------------------------------------------------------------------- CLI
+def read_id_list(path):
+    """lines of "<category> <model id>" -> {model id: category}"""
+    out = {}
+    with open(path) as fd:
+        for line in fd:
+            tok = line.split()
+            if len(tok) >= 2:
+                out[int(tok[1])] = tok[0]
+    return out
+
+
+def render_dataset(dataset, data_path, id_list, model_ids, views, save_path, camera_ranges=None, height=800, width=800, batch=16,
+                   seed=0, device=None, workers=8, echo=True):
+    """every model x camera range x render index: `batch` views per kernel batch (only the assets a batch shows are put into its
+    geometry tables), files written on host threads.  -> statistics (views, render_s, wall_s)"""
+    if dataset not in ('partnet', 'akb48'):
+        raise ValueError(f"dataset must be 'partnet' or 'akb48', got {dataset!r}")
+    t_start = time.perf_counter()
+    cats = read_id_list(id_list)
+    rng = np.random.RandomState(seed)
+    base = 'base' if dataset == 'partnet' else 'root'
+    jobs, assets = [], []
+    for mid in model_ids:
+        if mid not in cats:
+            raise ValueError(f"model {mid} is not listed in {id_list}")
+        cat = cats[mid]
+        path = os.path.join(data_path, str(mid)) if dataset == 'partnet' else os.path.join(data_path, cat, str(mid))
+        assets.append(load_asset(path, base_link_name=base))
+        for ci, rg in enumerate((camera_ranges or {}).get(cat, [DEFAULT_CAMERA_RANGE])):
+            for ri in range(views):
+                qpos = sample_qpos(assets[-1], rng)
+                jobs.append((RenderRequest(len(assets) - 1, qpos, sample_camera(rg, rng)),
+                             dict(model_id=mid, category=cat, camera_idx=ci, render_idx=ri)))
+    stats = dict(views=len(jobs), render_s=0.0)
+    os.makedirs(save_path, exist_ok=True)
+    batch = max(1, int(batch))
+    with ThreadPoolExecutor(max_workers=max(1, min(int(workers), 16))) as pool:
+        pending = []
+        for i in range(0, len(jobs), batch):
+            chunk = jobs[i:i + batch]
+            shown = sorted({r.asset for r, _ in chunk})
+            local = [RenderRequest(shown.index(r.asset), r.joint_qpos, r.camera_pos) for r, _ in chunk]
+            t0 = time.perf_counter()
+            out = render_views([assets[a] for a in shown], local, height, width, device=device)
+            stats['render_s'] += time.perf_counter() - t0
+            for (_, meta), view in zip(chunk, out):
+                name = f"{meta['category']}_{meta['model_id']}_{meta['camera_idx']}_{meta['render_idx']}"
+                pending.append(pool.submit(write_view, save_path, name, view, meta))
+                if echo:
+                    print(f'{name}: rendered')
+        for p in pending:
+            p.result()
+    stats['wall_s'] = time.perf_counter() - t_start
+    return stats
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--dataset', default='partnet', choices=('partnet', 'akb48'))
+    ap.add_argument('--data_path', required=True)
+    ap.add_argument('--id_list', required=True, help='lines of "<category> <model id>"')
+    ap.add_argument('--model_ids', type=int, nargs='+', required=True)
+    ap.add_argument('--views', type=int, default=1, help='render indices per model and camera range')
+    ap.add_argument('--camera_ranges', default=None,
+                    help='JSON: {category: [{theta_min, theta_max, phi_min, phi_max, distance_min, distance_max}, ...]}; '
+                         'categories it does not list use DEFAULT_CAMERA_RANGE')
+    ap.add_argument('--height', type=int, default=800)
+    ap.add_argument('--width', type=int, default=800)
+    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--save_path', required=True)
+    ap.add_argument('--device', default=None, help='cuda:0 (default when present) or cpu (the numpy path)')
+    args = ap.parse_args(argv)
+    ranges = None
+    if args.camera_ranges:
+        with open(args.camera_ranges) as fd:
+            ranges = json.load(fd)
+    stats = render_dataset(args.dataset, args.data_path, args.id_list, args.model_ids, args.views, args.save_path, ranges, args.height,
+                           args.width, args.batch, args.seed, args.device)
+    print(json.dumps(stats))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

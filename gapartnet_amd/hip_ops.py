@@ -1477,6 +1477,92 @@ def view_convert(depth, rgb, sem, ins, npcs, K, m, max_groups=0):
     return buf, layout
 
 
+# ---------------------------------------------------------------------------------------------------- RD (asset rendering)
+RENDER_COUNTERS = 5
+_RENDER_DT = {torch.float32: 4, torch.int32: 4, torch.uint8: 1}
+
+
+def render_layout(V, H, W, L):
+    """(name, dtype, shape, byte offset) of every result of render_batch inside its one buffer, and the buffer's size"""
+    fields = [("counters", torch.int32, (V, RENDER_COUNTERS)), ("link_area", torch.int32, (V, L)), ("link_inst", torch.int32, (V, L)),
+              ("depth", torch.float32, (V, H, W)), ("tri", torch.int32, (V, H, W)), ("sem", torch.int32, (V, H, W)),
+              ("ins", torch.int32, (V, H, W)), ("npcs", torch.float32, (V, H, W, 3)), ("rgb", torch.uint8, (V, H, W, 3))]
+    layout, total = [], 0
+    for name, dt, shape in fields:
+        layout.append((name, dt, shape, total))
+        total += (int(np.prod(shape)) * _RENDER_DT[dt] + 255) // 256 * 256
+    return layout, total
+
+
+def render_fields(buf, layout):
+    """views of a render_batch buffer (on the device or a host copy of it) by name"""
+    out = {}
+    for name, dt, shape, off in layout:
+        nbytes = int(np.prod(shape)) * _RENDER_DT[dt]
+        out[name] = buf[off:off + nbytes].view(dt).view(shape)
+    return out
+
+
+def render_max_links() -> int:
+    return int(_C.lib().gpn_render_max_links())
+
+
+def render_batch(geom, views, H, W, Nt_max, background=(0, 0, 0), timings=None, buf=None):
+    """V views of articulated assets -> depth, winning triangle, labels, NPCS and RGB (include/gpn.h section RD: setup, raster,
+    annotate; no host read in between).  geom: verts [Nv,3] f32, tris [Nt,3] i32, tri_visual / tri_link [Nt] i32, tri_color [Nt,3]
+    f32, assets [A,4] i32.  views: view_asset [V] i32, cam [V,20] f64, vis_mat [V,M,12] f64, link_cat / link_rank [V,L] i32,
+    link_frame [V,L,13] f64.  -> (buffer, layout): every result in ONE device buffer (render_fields names them).  timings: a list
+    that receives (start, end) torch events around each of the three entry points.  buf: a uint8 device buffer of the layout's
+    size to write into (default: a new one)."""
+    verts, tris = _c(geom["verts"], torch.float32), _c(geom["tris"], torch.int32)
+    tri_visual, tri_link = _c(geom["tri_visual"], torch.int32), _c(geom["tri_link"], torch.int32)
+    tri_color, assets = _c(geom["tri_color"], torch.float32), _c(geom["assets"], torch.int32)
+    view_asset, cam, vis_mat = _c(views["view_asset"], torch.int32), _c(views["cam"], torch.float64), _c(views["vis_mat"], torch.float64)
+    link_cat, link_rank = _c(views["link_cat"], torch.int32), _c(views["link_rank"], torch.int32)
+    link_frame = _c(views["link_frame"], torch.float64)
+    dev = _dev(verts, tris, tri_visual, tri_link, tri_color, assets, view_asset, cam, vis_mat, link_cat, link_rank, link_frame)
+    V, H, W, Nt_max = int(view_asset.shape[0]), int(H), int(W), int(Nt_max)
+    Nv, Nt, A = int(verts.shape[0]), int(tris.shape[0]), int(assets.shape[0])
+    if tuple(verts.shape) != (Nv, 3) or tuple(tris.shape) != (Nt, 3) or tri_visual.numel() != Nt or tri_link.numel() != Nt \
+            or tuple(tri_color.shape) != (Nt, 3) or tuple(assets.shape) != (A, 4):
+        raise _C.GpnError("render_batch: verts [Nv,3], tris [Nt,3], tri_visual / tri_link [Nt], tri_color [Nt,3], assets [A,4]")
+    if cam.numel() != V * 20 or vis_mat.dim() != 3 or vis_mat.shape[0] != V or vis_mat.shape[2] != 12 or link_cat.dim() != 2 \
+            or link_cat.shape[0] != V or link_rank.shape != link_cat.shape or link_frame.numel() != link_cat.numel() * 13:
+        raise _C.GpnError("render_batch: cam [V,20], vis_mat [V,M,12], link_cat / link_rank [V,L], link_frame [V,L,13]")
+    M, L = int(vis_mat.shape[1]), int(link_cat.shape[1])
+    layout, total = render_layout(V, H, W, L)
+    if buf is None:
+        buf = torch.empty((total,), dtype=torch.uint8, device=dev)
+    elif buf.dtype != torch.uint8 or buf.numel() != total or not buf.is_contiguous() or buf.device != dev:
+        raise _C.GpnError(f"render_batch: buf must be a contiguous uint8 tensor of {total} bytes on {dev}")
+    f = render_fields(buf, layout)
+    lib = _C.lib()
+    nbytes = lib.gpn_render_ws_bytes(i32(V), i32(Nt_max))
+    ws = _ws(nbytes, dev)
+    wsp, wsb = (ptr(ws), szt(ws.numel())) if nbytes else (ptr(None), szt(0))
+
+    def timed(call, what):
+        if timings is not None:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+        check(call(), what)
+        if timings is not None:
+            b.record()
+            timings.append((a, b))
+
+    timed(lambda: lib.gpn_render_setup(ptr(verts), i32(Nv), ptr(tris), ptr(tri_visual), i32(Nt), ptr(assets), i32(A), ptr(view_asset),
+                                       ptr(cam), ptr(vis_mat), i32(M), i32(V), i32(H), i32(W), i32(Nt_max), wsp, wsb,
+                                       ptr(f["counters"]), _stream()), "gpn_render_setup")
+    timed(lambda: lib.gpn_render_raster(ptr(assets), i32(A), ptr(view_asset), i32(Nt), i32(V), i32(H), i32(W), i32(Nt_max), wsp, wsb,
+                                        ptr(f["depth"]), ptr(f["tri"]), _stream()), "gpn_render_raster")
+    timed(lambda: lib.gpn_render_annotate(ptr(f["depth"]), ptr(f["tri"]), ptr(tri_link), ptr(tri_color), i32(Nt), ptr(assets), i32(A),
+                                          ptr(view_asset), ptr(cam), ptr(link_cat), ptr(link_rank), ptr(link_frame), i32(L), i32(V),
+                                          i32(H), i32(W), i32(Nt_max), wsp, wsb, i32(background[0]), i32(background[1]),
+                                          i32(background[2]), ptr(f["link_area"]), ptr(f["link_inst"]), ptr(f["sem"]), ptr(f["ins"]),
+                                          ptr(f["npcs"]), ptr(f["rgb"]), _stream()), "gpn_render_annotate")
+    return buf, layout
+
+
 # ---------------------------------------------------------------------------------------------------- CP (raw clouds)
 CLOUD_OK, CLOUD_FEW, CLOUD_EMPTY, CLOUD_DEGENERATE = 0, 1, 2, 3
 

@@ -860,6 +860,63 @@ int gpn_cloud_nearest(const float* points, int64_t M, int stride, const int64_t*
                       gpn_stream_t stream);
 
 /* ================================================================================================
+ * RD - articulated assets -> training views (the reference's dataset/render_tools/render.py without SAPIEN): z-depth, the winning
+ * triangle, link labels, the NPCS map and a flat-shaded RGB image for a batch of V views of one size H x W (H, W <= 16384, V <=
+ * 65535).  Views may show different assets.  No host read between the launches; no float atomics; every pixel is stored once, so
+ * the images do not depend on launch order.  All float64 arithmetic is uncontracted and in the order written here.
+ * Geometry, uploaded once per asset set: verts [Nv,3] f32 as parsed, tris [Nt,3] i32 (rows of verts), tri_visual [Nt] i32 and
+ *   tri_link [Nt] i32 (the visual / link of the triangle, counted inside its asset), tri_color [Nt,3] f32 in [0,1],
+ *   assets [A,4] i32 = (first triangle, triangle count, visual count, link count).  DECISION: links are numbered inside their
+ *   asset because every per-link table below is per view, so the table needs no first-link column.
+ * Per view: view_asset [V] i32; cam [V,20] f64 = fx fy cx cy | R [3,3] row-major = meta world2camera_rotation | t [3] = meta
+ *   camera2world_translation | the light direction in the camera frame [3] (unit) | pad; vis_mat [V,M,3,4] f64 = world-to-camera
+ *   * link pose * visual origin of every visual (composed on the host), camera point = ((m0 x + m1 y) + m2 z) + m3 per row;
+ *   link_cat [V,L] i32 (category id, -1 for a link that is no target), link_rank [V,L] i32 (position in the annotation file),
+ *   link_frame [V,L,13] f64 = T [3] | scaler | R [3,3] row-major, the NPCS frame of get_NPCS_map_from_oriented_bbox.
+ * DECISION: pixel (x, y) samples the ray through u = x, v = y - the ray the reference's own back-projection (x - cx) z / fx
+ *   assumes, so back-projected points lie on the mesh.
+ * gpn_render_setup, one thread per (view, triangle): u = (fx X) / Z + cx, v = (fy Y) / Z + cy, snapped to rint(u * 256) (half to
+ *   even), 1 / Z kept as f64; the triangle is oriented to positive doubled area in int64 (no back-face culling: PartNet meshes are
+ *   not consistently wound).  Dropped and counted in counters [V, GPN_RENDER_COUNTERS] i32 (zeroed here), first rule that applies:
+ *   an index outside its table (DROP_INDEX); any vertex with Z < 0.1 or NaN (DROP_NEAR; DECISION: the whole triangle goes, cameras
+ *   sit 3.5 to 4.5 units away); a snapped coordinate outside +-16384 px (DROP_GUARD); zero doubled area (DROP_ZERO_AREA); a pixel
+ *   box that holds no pixel centre of the image (DROP_OFFSCREEN).  Writes one 64-byte record (snapped vertices, three 1 / Z, shade, clipped pixel
+ *   box) and one 8-byte box per (view, triangle slot) into the workspace; Nt_max = the largest triangle count of a view's asset.
+ * gpn_render_raster, one 256-lane workgroup per 16 x 16 tile per view, one pixel per lane: the boxes are scanned in chunks of 256,
+ *   hits are compacted in triangle order into LDS by wave ballots, then every lane walks the list.  Coverage: int64 edge
+ *   functions E(a,b,p) = (bx - ax)(py - ay) - (by - ay)(px - ax) at p = (256 x, 256 y), all >= 0, an E == 0 edge counts only when
+ *   it runs up (dy < 0) or level to the right (dy == 0, dx > 0) - the top-left rule: a shared edge belongs to one triangle.
+ *   li = (double)Ei / (double)(E0 + E1 + E2), invz = (l0 iz0 + l1 iz1) + l2 iz2, winner = largest invz, ties to the lowest
+ *   triangle.  depth [V,H,W] f32 = (float)(1 / invz), 0 where empty; tri [V,H,W] i32 = row of tris, -1 where empty.
+ * gpn_render_annotate: link_area [V,L] i32 = pixels won per link; link_inst [V,L] i32 = 0, 1, ... in link_rank order over the
+ *   target links with area > 0, -1 otherwise (render_sem_ins_seg_map's part_ins_cnt loop); sem / ins [V,H,W] i32 = -2 where |depth|
+ *   < 1e-6, -1 on a non-target link, else category / instance id; npcs [V,H,W,3] f32 where ins >= 0, else 0: pc = (((x - cx) z)
+ *   / fx, ((y - cy) z) / fy, z) with z = (double)depth, w_r = ((pc0 R[r][0] + pc1 R[r][1]) + pc2 R[r][2]) + t_r, g = (w - T) /
+ *   scaler, npcs_r = (float)((g0 Rl[r][0] + g1 Rl[r][1]) + g2 Rl[r][2]); rgb [V,H,W,3] u8 = the background where empty, else
+ *   clip(rint((colour * shade) * 255)), shade = 0.5 + 0.5 |n . l| / |n| with n the float64 camera-space cross product (v1 - v0) x
+ *   (v2 - v0).  RGB is an approximation of the reference's renderer (no textures, point lights or shadows), not a contract.
+ * L <= gpn_render_max_links().  V == 0 and Nt_max == 0 are valid (empty images).
+ * ================================================================================================ */
+#define GPN_RENDER_COUNTERS 5
+#define GPN_RENDER_DROP_INDEX 0
+#define GPN_RENDER_DROP_NEAR 1
+#define GPN_RENDER_DROP_GUARD 2
+#define GPN_RENDER_DROP_ZERO_AREA 3
+#define GPN_RENDER_DROP_OFFSCREEN 4
+int gpn_render_max_links(void);
+size_t gpn_render_ws_bytes(int V, int Nt_max);
+int gpn_render_setup(const float* verts, int Nv, const int32_t* tris, const int32_t* tri_visual, int Nt, const int32_t* assets,
+                     int A, const int32_t* view_asset, const double* cam, const double* vis_mat, int M, int V, int H, int W,
+                     int Nt_max, void* ws, size_t ws_bytes, int32_t* counters, gpn_stream_t stream);
+int gpn_render_raster(const int32_t* assets, int A, const int32_t* view_asset, int Nt, int V, int H, int W, int Nt_max,
+                      const void* ws, size_t ws_bytes, float* depth, int32_t* tri, gpn_stream_t stream);
+int gpn_render_annotate(const float* depth, const int32_t* tri, const int32_t* tri_link, const float* tri_color, int Nt,
+                        const int32_t* assets, int A, const int32_t* view_asset, const double* cam, const int32_t* link_cat,
+                        const int32_t* link_rank, const double* link_frame, int L, int V, int H, int W, int Nt_max, const void* ws,
+                        size_t ws_bytes, int bg_r, int bg_g, int bg_b, int32_t* link_area, int32_t* link_inst, int32_t* sem,
+                        int32_t* ins, float* npcs, uint8_t* rgb, gpn_stream_t stream);
+
+/* ================================================================================================
  * PF - pose fitting.  replaces the per-proposal numpy loop of gapartnet/misc/pose_fitting.py:4-147 (estimate_pose_from_npcs:
  * 5-point RANSAC over Umeyama similarity fits, Umeyama on the inliers, NPCS-aligned box; callers network/model.py:966-980,
  * structure/utils.py:172-188) for ALL proposals of a batch: two launches, float64 like the reference.
