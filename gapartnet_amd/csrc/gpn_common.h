@@ -187,21 +187,17 @@ inline size_t stat_slab_bytes(int C) { return align_up((size_t)kStatSlots * 4 * 
 int spconv_fwd_into(const float* in, const float* packed_w, const int32_t* nbr, const int32_t* nbr_p, const int32_t* perm, int K,
                     int64_t n_dst, int cin, int cout, float* out, int accumulate, const ConvStats& stats, void* ws,
                     size_t ws_bytes, hipStream_t stream, const DevRows& rows = DevRows());
-// true if a conv of this shape runs on a kernel whose epilogue can accumulate ConvStats (masked-tile or direct kernel)
-bool spconv_fwd_accumulates_stats(int K, int64_t n_dst, int cin, int cout);
-bool spconv_fwd_accumulates_stats(int K, int64_t n_dst, int cin, int cout, const DevRows& rows);
-// true if a conv of this shape runs on a kernel whose epilogue can apply a ConvAffine (an inference pass's BatchNorm)
-bool spconv_fwd_applies_affine(int K, int64_t n_dst, int cin, int cout, const DevRows& rows);
-// the masked-tile kernel (spconv_tiles.hip): which shapes it takes, and its launch
-bool spconv_tiles_supported(int K, int64_t n_dst, int cin, int cout);
-int spconv_tiles_launch(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                        int cin, int cout, int accumulate, const ConvStats& stats, float* out, hipStream_t stream,
-                        const DevRows& rows = DevRows());
-// the masked tap-split kernel (spconv_msplit.hip, round 6): k = 27 / 8 layers below the masked-tile kernel's size
-bool spconv_msplit_supported(int K, int64_t n_dst, int cin, int cout);
-int spconv_msplit_launch(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                         int cin, int cout, int accumulate, const ConvStats& stats, float* out, hipStream_t stream,
-                         const DevRows& rows = DevRows());
+// Which kernel a conv of this shape takes and what that kernel's epilogue can do: decided ONCE, by spconv_fwd_route
+// (spconv_fwd.hip); spconv_fwd_into launches by it and the network executor plans by it (workspaces, BatchNorm sum slabs, folded
+// BatchNorms).  With device-counted rows n_dst is the bound and the decision also holds for the host's plan.
+struct ConvRoute {
+  enum Kind { kNone, kTiles, kMsplit, kDirect, kLockstep, kUnroutable };  // kNone: nothing to do; kUnroutable: GPN_ERR_ARG
+  Kind kind = kNone;
+  bool sums = false;    // the epilogue can accumulate ConvStats (masked-tile, masked tap-split, direct)
+  bool affine = false;  // the epilogue can apply a ConvAffine (masked-tile, masked tap-split, direct for k = 1)
+  size_t ws_bytes = 0;  // the lock-step kernel's partial sums, else 0
+};
+ConvRoute spconv_fwd_route(int K, int64_t n_dst, int cin, int cout, const DevRows& rows = DevRows());
 // the bf16 inference path (spconv_bf16.hip): argument check, conv launch, batched weight packing and the elementwise launches the
 // network executor's bf16 pass (net.hip, gpn_net_forward_bf16) is made of
 struct PackBf16Desc {

@@ -363,7 +363,7 @@ int net_forward_impl(const char* who, const gpn_net_op_t* ops, int n_ops, const 
         const gpn_net_conv_t& cv = nets[t].convs[cv_op.param];
         const gpn_net_slot_t& out_slot = nets[0].slots[cv_op.dst];
         if (!gpn::bn_two_pass(plan_of(out_slot), cv.cout) ||
-            !gpn::spconv_fwd_accumulates_stats(rb.K, rb.n_dst, cv.cin, cv.cout, dev_rows(out_slot)))
+            !gpn::spconv_fwd_route(rb.K, rb.n_dst, cv.cin, cv.cout, dev_rows(out_slot)).sums)
           continue;
         slab_of[t][i] = slab_of[t][i + 1] = reinterpret_cast<unsigned long long*>(area + off);
         off += gpn::stat_slab_bytes(cv.cout);
@@ -389,7 +389,7 @@ int net_forward_impl(const char* who, const gpn_net_op_t* ops, int n_ops, const 
       if (bn_op.src1 == cv_op.dst || bn_op.dst == cv_op.src0) continue;
       const gpn_net_rulebook_t& rb = rbs[cv_op.rulebook];
       const gpn_net_conv_t& cv = nets[0].convs[cv_op.param];
-      bool ok = gpn::spconv_fwd_applies_affine(rb.K, rb.n_dst, cv.cin, cv.cout, dev_rows(nets[0].slots[cv_op.dst]));
+      bool ok = gpn::spconv_fwd_route(rb.K, rb.n_dst, cv.cin, cv.cout, dev_rows(nets[0].slots[cv_op.dst])).affine;
       for (int t = 0; t < n_nets; ++t) {
         const gpn_net_bn_t& bn = nets[t].bns[bn_op.param];
         ok = ok && bn.running_mean && bn.running_var && bn.eps == nets[0].bns[bn_op.param].eps;
@@ -818,7 +818,7 @@ int net_backward_impl(const char* who, const gpn_net_op_t* ops, int n_ops, const
       const gpn_net_conv_t& cv = nets[0].convs[ops[i].param];
       const gpn_net_slot_t& in_slot = nets[0].slots[ops[i].src0];
       if (!gpn::bn_two_pass(plan_of(in_slot), cv.cin) ||
-          !gpn::spconv_fwd_accumulates_stats(rb.K, rb.n_src, cv.cout, cv.cin, dev_rows(in_slot)))
+          !gpn::spconv_fwd_route(rb.K, rb.n_src, cv.cout, cv.cin, dev_rows(in_slot)).sums)
         continue;
       for (int t = 0; t < n_nets; ++t)
         bn_slab[t][j] = reinterpret_cast<unsigned long long*>(base + t * per_net + need.tmp + need.packed + off);

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "gpn_common.h"
+#include "spconv_dispatch.h"  // (the instantiation lists)
 #include "spconv_pack.h"
 
 namespace {
@@ -330,10 +331,10 @@ template <int CT>
 int dispatch_wgrad_nt(int nt, const gpn::WgradSets& sets, int K, int64_t n_dst, int cin, int S, hipStream_t stream,
                       const int64_t* n_dev) {
   switch (nt) {
-#define GPN_CASE(N) \
+#define GPN_X(N) \
   case N: return launch_wgrad<CT, N>(sets, K, n_dst, cin, S, stream, n_dev);
-    GPN_CASE(1) GPN_CASE(2) GPN_CASE(3) GPN_CASE(4) GPN_CASE(5) GPN_CASE(6) GPN_CASE(7) GPN_CASE(8)
-#undef GPN_CASE
+    GPN_WGRAD_NT(GPN_X)
+#undef GPN_X
     default:
       gpn::set_error("gpn_spconv_wgrad: cout=%d not supported (multiple of 16, <= 128)", nt * 16);
       return GPN_ERR_ARG;
@@ -457,12 +458,11 @@ int wgrad_contract(const WgradSets& sets, int K, int64_t n_dst, int cin, int cou
   const int CT = ct_tiles < 4 ? ct_tiles : 4;
   const int nt = cout / 16;
   gpn::ProfScope prof(GPN_K_SPCONV_WGRAD, stream, 0.0, 0.0);
-  switch (CT) {
-    case 1: return dispatch_wgrad_nt<1>(nt, sets, K, n_dst, cin, S, stream, n_dst_dev);
-    case 2: return dispatch_wgrad_nt<2>(nt, sets, K, n_dst, cin, S, stream, n_dst_dev);
-    case 3: return dispatch_wgrad_nt<3>(nt, sets, K, n_dst, cin, S, stream, n_dst_dev);
-    default: return dispatch_wgrad_nt<4>(nt, sets, K, n_dst, cin, S, stream, n_dst_dev);
-  }
+#define GPN_X(ct) if (CT == ct) return dispatch_wgrad_nt<ct>(nt, sets, K, n_dst, cin, S, stream, n_dst_dev);
+  GPN_WGRAD_CT(GPN_X)
+#undef GPN_X
+  gpn::set_error("gpn_spconv_wgrad: cin=%d not supported (a multiple of 16)", cin);
+  return GPN_ERR_ARG;
 }
 
 WgradReduceJob wgrad_reduce_job(const float* partial, int S, int K, int cin, int cout, int flags, float* dW) {

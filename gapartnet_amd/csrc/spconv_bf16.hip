@@ -32,7 +32,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "gpn_common.h"
+#include "spconv_dispatch.h"  // (the instantiation lists)
 
 namespace {
 
@@ -236,28 +236,14 @@ int launch_bf16(const Bf16ConvArgs& a, hipStream_t stream) {
   return GPN_OK;
 }
 
-// input widths (16-channel blocks) the kernel is instantiated for: those of a residual U-Net with channels 16 (l + 1),
-// l < 7, and of its decoder convs behind the skip concats (2c -> c)
-#define GPN_BF16_CB(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(10) X(12) X(14)
-
+// (instantiated for the fp32 masked-tile kernel's input widths and column tiles per wave: GPN_CONV_CB x GPN_TILES_NT)
 template <int CB>
 int dispatch_cols(int NT, const Bf16ConvArgs& a, hipStream_t stream) {
-  switch (NT) {
-    case 1: return launch_bf16<CB, 1>(a, stream);
-    case 2: return launch_bf16<CB, 2>(a, stream);
-    case 3: return launch_bf16<CB, 3>(a, stream);
-    case 4: return launch_bf16<CB, 4>(a, stream);
-    case 5: return launch_bf16<CB, 5>(a, stream);
-    case 6: return launch_bf16<CB, 6>(a, stream);
-    default: return launch_bf16<CB, 7>(a, stream);
-  }
-}
-
-bool supported_width(int CB) {
-#define GPN_X(cb) if (CB == cb) return true;
-  GPN_BF16_CB(GPN_X)
+#define GPN_X(nt) if (NT == nt) return launch_bf16<CB, nt>(a, stream);
+  GPN_TILES_NT(GPN_X)
 #undef GPN_X
-  return false;
+  gpn::set_error("gpn_spconv_fwd_bf16: no bf16 kernel for %d column tiles per wave", NT);
+  return GPN_ERR_ARG;
 }
 
 // column tiles per wave: the widest divisor (<= 7) of the layer's column tiles - a function of the shape alone
@@ -351,7 +337,7 @@ int spconv_bf16_check(const char* who, int K, int64_t n_dst, int cin, int cout) 
     gpn::set_error("%s: channel counts must be multiples of 16 (cin = %d, cout = %d)", who, cin, cout);
     return GPN_ERR_ARG;
   }
-  if (!supported_width(cin / 16)) {
+  if (!conv_width(cin / 16)) {
     gpn::set_error("%s: no bf16 kernel for %d input channels (16 ... 128, 160, 192, 224)", who, cin);
     return GPN_ERR_ARG;
   }
@@ -378,7 +364,7 @@ int spconv_bf16_launch(const uint16_t* in, const uint16_t* packed, const int32_t
   gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 2.0 * pairs * cin * cout, (double)n_dst * (cin + cout) * 2.0,
                       gpn::prof_shape_tag(K, n_dst, cin, cout, false));
 #define GPN_X(cb) if (CB == cb) return dispatch_cols<cb>(NT, a, stream);
-  GPN_BF16_CB(GPN_X)
+  GPN_CONV_CB(GPN_X)
 #undef GPN_X
   gpn::set_error("gpn_spconv_fwd_bf16: no bf16 kernel for %d -> %d channels", cin, cout);
   return GPN_ERR_ARG;

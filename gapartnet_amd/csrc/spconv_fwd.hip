@@ -25,7 +25,7 @@
 #include <cstdlib>
 
 #include "bn_stats.h"
-#include "gpn_common.h"
+#include "spconv_dispatch.h"
 
 namespace {
 
@@ -235,36 +235,37 @@ FwdPlan plan_fwd(int K, int64_t n_dst, int cin, int cout) {
 }
 
 template <int NTW, int CW, int NS>
-int launch_fwd(const FwdPlan& p, const float* in, const float* packed, const int32_t* nbr, int K, int64_t n_dst,
-               int cin, int nt_total, int accumulate, float* out, hipStream_t stream) {
-  const int64_t tiles = gpn::cdiv(n_dst, 16);
-  const dim3 grid((unsigned)gpn::cdiv(tiles, p.wpb), (unsigned)gpn::cdiv(nt_total, NTW), (unsigned)p.splits);
+int launch_fwd(const FwdPlan& p, const gpn::ConvCall& c) {
+  const int nt_total = c.cout / 16;
+  const dim3 grid((unsigned)gpn::cdiv(gpn::cdiv(c.n_dst, 16), p.wpb), (unsigned)gpn::cdiv(nt_total, NTW), (unsigned)p.splits);
   const size_t lds = FwdCfg<NTW, CW>::lds_bytes;
-  hipLaunchKernelGGL((spconv_fwd_kernel<NTW, CW, NS>), grid, dim3(p.wpb * 64), lds, stream, in, packed, nbr, K, n_dst,
-                     cin, nt_total, p.taps_per_split, accumulate, out);
+  hipLaunchKernelGGL((spconv_fwd_kernel<NTW, CW, NS>), grid, dim3(p.wpb * 64), lds, c.stream, c.in, c.packed, c.nbr, c.K, c.n_dst,
+                     c.cin, nt_total, p.taps_per_split, c.accumulate, c.out);
   GPN_CHECK_LAUNCH();
   return GPN_OK;
 }
 
 template <int NTW, int CW>
-int dispatch_ns(const FwdPlan& p, const float* in, const float* packed, const int32_t* nbr, int K, int64_t n_dst,
-                int cin, int nt_total, int accumulate, float* out, hipStream_t stream) {
-  // NS = ceil(CW NTW / waves per workgroup) and plan_fwd gives 4, 8 or 16 waves: only those three values are instantiated
-  constexpr int X = CW * NTW, NS4 = (X + 3) / 4, NS8 = (X + 7) / 8, NS16 = (X + 15) / 16;
-  const int ns = (int)gpn::cdiv(X, p.wpb);
-  if (ns == NS4) return launch_fwd<NTW, CW, NS4>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-  if (ns == NS8) return launch_fwd<NTW, CW, NS8>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-  return launch_fwd<NTW, CW, NS16>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
+int dispatch_ns(const FwdPlan& p, const gpn::ConvCall& c) {  // NS = slab float4 per thread = ceil(CW NTW / waves per workgroup)
+#define GPN_X(w) if (p.wpb == w) return launch_fwd<NTW, CW, (CW * NTW + w - 1) / w>(p, c);
+  GPN_LOCKSTEP_WAVES(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("lock-step", c);
 }
 
 template <int NTW>
-int dispatch_cw(const FwdPlan& p, const float* in, const float* packed, const int32_t* nbr, int K, int64_t n_dst,
-                int cin, int nt_total, int accumulate, float* out, hipStream_t stream) {
-  switch (p.cw) {
-    case 1: return dispatch_ns<NTW, 1>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-    case 2: return dispatch_ns<NTW, 2>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-    default: return dispatch_ns<NTW, 4>(p, in, packed, nbr, K, n_dst, cin, nt_total, accumulate, out, stream);
-  }
+int dispatch_cw(const FwdPlan& p, const gpn::ConvCall& c) {
+#define GPN_X(v) if (p.cw == v) return dispatch_ns<NTW, v>(p, c);
+  GPN_LOCKSTEP_CW(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("lock-step", c);
+}
+
+int launch_lockstep(const FwdPlan& p, const gpn::ConvCall& c) {
+#define GPN_X(v) if (p.ntw == v) return dispatch_cw<v>(p, c);
+  GPN_LOCKSTEP_NTW(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("lock-step", c);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -684,64 +685,58 @@ constexpr int64_t kSplit4Units = 12000, kSplit2Units = 0;
 std::atomic<int64_t> g_split4_units{kSplit4Units};
 std::atomic<int64_t> g_split2_units{kSplit2Units};
 
+int64_t split_below_units(int ways) { return (ways == 4 ? g_split4_units : g_split2_units).load(std::memory_order_relaxed); }
+
 template <int KT, int CB, int SP>
-int launch_split(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int64_t n_dst, int nt_total,
-                 int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream, const gpn::DevRows& rows) {
-  if (stats.ep.mean) {
+int launch_split(const gpn::ConvCall& c) {
+  if (c.stats.ep.mean) {
     gpn::set_error("gpn_spconv_fwd: the direct kernel's tap-split form has no BatchNorm epilogue");
     return GPN_ERR_ARG;
   }
-  const int64_t units = gpn::cdiv(n_dst, 16) * nt_total;
-  const int64_t plan_units = gpn::cdiv(gpn::plan_rows(n_dst, rows), 16) * nt_total;
+  const int nt_total = c.cout / 16;
+  const int64_t units = gpn::cdiv(c.n_dst, 16) * nt_total;
+  const int64_t plan_units = gpn::cdiv(gpn::plan_rows(c.n_dst, c.rows), 16) * nt_total;
   const size_t packed_bytes = (size_t)KT * CB * nt_total * 1024;
-  const dim3 grid(gpn::dev_grid(gpn::cdiv(units, 4 / SP), gpn::cdiv(plan_units, 4 / SP), rows.dev != nullptr, 8), stats.twin.in ? 2 : 1);
-  if (rows.dev)
-    hipLaunchKernelGGL((spconv_fwd_split_kernel<KT, CB, SP, true>), grid, dim3(256), 0, stream, in, packed, nbr, n_dst, nt_total, units,
-                       packed_bytes, perm, accumulate, stats, out, rows.dev);
-  else
-    hipLaunchKernelGGL((spconv_fwd_split_kernel<KT, CB, SP, false>), grid, dim3(256), 0, stream, in, packed, nbr, n_dst, nt_total, units,
-                       packed_bytes, perm, accumulate, stats, out, rows.dev);
+  const dim3 grid(gpn::dev_grid(gpn::cdiv(units, 4 / SP), gpn::cdiv(plan_units, 4 / SP), c.rows.dev != nullptr, 8), c.stats.twin.in ? 2 : 1);
+  gpn::with_bool(c.rows.dev != nullptr, [&](auto dev) {
+    hipLaunchKernelGGL((spconv_fwd_split_kernel<KT, CB, SP, decltype(dev)::value>), grid, dim3(256), 0, c.stream, c.in, c.packed, c.nbr,
+                       c.n_dst, nt_total, units, packed_bytes, c.perm, c.accumulate, c.stats, c.out, c.rows.dev);
+  });
   GPN_CHECK_LAUNCH();
   return GPN_OK;
 }
 
 template <int KT, int CB>
-int launch_direct(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int64_t n_dst, int nt_total,
-                  int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream, const gpn::DevRows& rows) {
-  const int64_t units = gpn::cdiv(n_dst, 16) * nt_total;
-  const int64_t plan_units = gpn::cdiv(gpn::plan_rows(n_dst, rows), 16) * nt_total;  // (the form is picked from the planned count)
-  if constexpr (KT >= 8) {  // (a k = 1 layer has no taps to split)
-    if (plan_units < g_split4_units.load(std::memory_order_relaxed))
-      return launch_split<KT, CB, 4>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    if (plan_units < g_split2_units.load(std::memory_order_relaxed))
-      return launch_split<KT, CB, 2>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
+int launch_direct(const gpn::ConvCall& c) {
+  const int nt_total = c.cout / 16;
+  const int64_t units = gpn::cdiv(c.n_dst, 16) * nt_total;
+  const int64_t plan_units = gpn::cdiv(gpn::plan_rows(c.n_dst, c.rows), 16) * nt_total;  // (the form is picked from the planned count)
+  if constexpr (KT >= gpn::kSplitMinTaps) {
+#define GPN_X(ways) if (plan_units < split_below_units(ways)) return launch_split<KT, CB, ways>(c);
+    GPN_SPLIT_WAYS(GPN_X)
+#undef GPN_X
   }
-  const size_t packed_bytes = (size_t)KT * CB * nt_total * 1024;
-  const dim3 grid(gpn::dev_grid(gpn::cdiv(units, 4), gpn::cdiv(plan_units, 4), rows.dev != nullptr, 8), stats.twin.in ? 2 : 1);
-  if constexpr (KT == 1) {
-    if (stats.ep.mean) {  // (an inference pass: the BatchNorm behind the k = 1 conv in the epilogue)
-      if (rows.dev)
-        hipLaunchKernelGGL((spconv_fwd_direct_kernel<KT, CB, true, true>), grid, dim3(256), 0, stream, in, packed, nbr, n_dst, nt_total, units,
-                           packed_bytes, perm, accumulate, stats, out, rows.dev);
-      else
-        hipLaunchKernelGGL((spconv_fwd_direct_kernel<KT, CB, false, true>), grid, dim3(256), 0, stream, in, packed, nbr, n_dst, nt_total, units,
-                           packed_bytes, perm, accumulate, stats, out, rows.dev);
-      GPN_CHECK_LAUNCH();
-      return GPN_OK;
-    }
-  }
-  if (stats.ep.mean) {
+  if (KT != 1 && c.stats.ep.mean) {
     gpn::set_error("gpn_spconv_fwd: the direct kernel applies a BatchNorm in its epilogue for k = 1 layers only");
     return GPN_ERR_ARG;
   }
-  if (rows.dev)
-    hipLaunchKernelGGL((spconv_fwd_direct_kernel<KT, CB, true, false>), grid, dim3(256), 0, stream, in, packed, nbr, n_dst, nt_total, units,
-                       packed_bytes, perm, accumulate, stats, out, rows.dev);
-  else
-    hipLaunchKernelGGL((spconv_fwd_direct_kernel<KT, CB, false, false>), grid, dim3(256), 0, stream, in, packed, nbr, n_dst, nt_total, units,
-                       packed_bytes, perm, accumulate, stats, out, rows.dev);
+  const size_t packed_bytes = (size_t)KT * CB * nt_total * 1024;
+  const dim3 grid(gpn::dev_grid(gpn::cdiv(units, 4), gpn::cdiv(plan_units, 4), c.rows.dev != nullptr, 8), c.stats.twin.in ? 2 : 1);
+  // (EP, k = 1 only: an inference pass, the BatchNorm behind the conv in the epilogue)
+  gpn::with_bools(c.rows.dev != nullptr, c.stats.ep.mean != nullptr, [&](auto dev, auto ep) {
+    hipLaunchKernelGGL((spconv_fwd_direct_kernel<KT, CB, decltype(dev)::value, KT == 1 && decltype(ep)::value>), grid, dim3(256), 0,
+                       c.stream, c.in, c.packed, c.nbr, c.n_dst, nt_total, units, packed_bytes, c.perm, c.accumulate, c.stats, c.out,
+                       c.rows.dev);
+  });
   GPN_CHECK_LAUNCH();
   return GPN_OK;
+}
+
+bool direct_width(int CB) {
+#define GPN_X(cb) if (CB == cb) return true;
+  GPN_DIRECT_CB(GPN_X)
+#undef GPN_X
+  return false;
 }
 
 // which shapes take the direct variant.  Measured on the bench shapes (8 x 20k-point scenes; tools/kernel_rooflines.py, us per
@@ -750,32 +745,26 @@ int launch_direct(const float* in, const float* packed, const int32_t* nbr, cons
 // a layer has too few (tile, column) units to fill the chip and the tap-split lock-step kernel stays in use; so do the
 // k = 1 layers and input widths the unrolled stage loop is not instantiated for.
 bool use_direct(int K, int64_t n_dst, int cin, int cout) {
-  const int CB = cin / 16;
   // k = 1 layers (the residual blocks' shortcut convs, linear heads) take it too since round 3: its epilogue carries the
   // BatchNorm sums (bn_stats.h), the lock-step kernel's does not
   if (!(K == 27 || K == 8 || K == 1)) return false;
-  if (!(CB >= 1 && (CB <= 8 || CB == 10 || CB == 12))) return false;
-  // 32-bit byte offsets: source rows (at most 8 n_dst of them, for a stride-2 conv), output rows, the neighbour table
-  if (n_dst * (int64_t)8 * std::max(cin, cout) * 4 >= ((int64_t)1 << 31) || (int64_t)K * n_dst * 4 >= ((int64_t)1 << 31)) return false;
+  if (!direct_width(cin / 16) || !gpn::conv_offsets_fit32(K, n_dst, cin, cout)) return false;
   return gpn::cdiv(n_dst, 16) >= 16;
 }
 
 template <int KT>
-int dispatch_direct(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int64_t n_dst, int cin,
-                    int nt_total, int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream,
-                    const gpn::DevRows& rows) {
-  switch (cin / 16) {
-    case 1: return launch_direct<KT, 1>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 2: return launch_direct<KT, 2>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 3: return launch_direct<KT, 3>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 4: return launch_direct<KT, 4>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 5: return launch_direct<KT, 5>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 6: return launch_direct<KT, 6>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 7: return launch_direct<KT, 7>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 8: return launch_direct<KT, 8>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 10: return launch_direct<KT, 10>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    default: return launch_direct<KT, 12>(in, packed, nbr, perm, n_dst, nt_total, accumulate, stats, out, stream, rows);
-  }
+int dispatch_direct(const gpn::ConvCall& c) {
+#define GPN_X(cb) if (c.cin / 16 == cb) return launch_direct<KT, cb>(c);
+  GPN_DIRECT_CB(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("direct", c);
+}
+
+int direct_launch(const gpn::ConvCall& c) {
+#define GPN_X(kt) if (c.K == kt) return dispatch_direct<kt>(c);
+  GPN_DIRECT_KT(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("direct", c);
 }
 
 }  // namespace
@@ -796,12 +785,38 @@ extern "C" int gpn_probe_split_trace(void* buf) {
 }
 #endif
 
+// The ONE routing decision: masked-tile, else masked tap-split, else direct (or its tap-split form), else lock-step.  With
+// device-counted rows n_dst is the buffers' bound: the layer must fit the 32-bit offsets there, the masked-tile kernel must also
+// be the choice for the host's plan, the direct kernel's size floor is waived (max(n_dst, 256): 16 row tiles) and the lock-step
+// kernel is out - it sizes partial outputs from the row count.  The masked tap-split kernel does not look at the plan (pick_cut).
+gpn::ConvRoute gpn::spconv_fwd_route(int K, int64_t n_dst, int cin, int cout, const gpn::DevRows& rows) {
+  ConvRoute r;
+  if (n_dst <= 0) return r;
+  if (K < 1 || cin < 16 || cout < 16) r.kind = ConvRoute::kUnroutable;  // (spconv_fwd_into has refused these before it asks)
+  else if (spconv_tiles_supported(K, n_dst, cin, cout) && (!rows.dev || spconv_tiles_supported(K, plan_rows(n_dst, rows), cin, cout)))
+    r.kind = ConvRoute::kTiles;
+  else if (spconv_msplit_supported(K, n_dst, cin, cout)) r.kind = ConvRoute::kMsplit;
+  else if (use_direct(K, rows.dev ? std::max<int64_t>(n_dst, 256) : n_dst, cin, cout)) r.kind = ConvRoute::kDirect;
+  else if (rows.dev) r.kind = ConvRoute::kUnroutable;
+  else {
+    r.kind = ConvRoute::kLockstep;
+    const FwdPlan p = plan_fwd(K, n_dst, cin, cout);
+    if (p.splits > 1) r.ws_bytes = align_up((size_t)p.splits * n_dst * cout * sizeof(float));
+  }
+  r.sums = r.kind == ConvRoute::kTiles || r.kind == ConvRoute::kMsplit || r.kind == ConvRoute::kDirect;
+  r.affine = r.kind == ConvRoute::kTiles || r.kind == ConvRoute::kMsplit || (r.kind == ConvRoute::kDirect && K == 1);
+  return r;
+}
+
+// kind | sums << 8 | affine << 9 of the route; n_plan < 0: host-counted rows, else device-counted rows with that plan
+extern "C" int gpn_spconv_fwd_route(int K, int64_t n_dst, int64_t n_plan, int cin, int cout) {
+  static const int64_t counted = 0;  // (only its address is used: "the rows are a device counter")
+  const gpn::ConvRoute r = gpn::spconv_fwd_route(K, n_dst, cin, cout, n_plan < 0 ? gpn::DevRows() : gpn::DevRows{&counted, n_plan});
+  return (int)r.kind | (r.sums ? 1 << 8 : 0) | (r.affine ? 1 << 9 : 0);
+}
+
 extern "C" size_t gpn_spconv_fwd_ws_bytes(int K, int64_t n_dst, int cin, int cout) {
-  if (n_dst <= 0 || cin < 16 || cout < 16) return 0;
-  if (gpn::spconv_tiles_supported(K, n_dst, cin, cout) || gpn::spconv_msplit_supported(K, n_dst, cin, cout) || use_direct(K, n_dst, cin, cout))
-    return 0;
-  const FwdPlan p = plan_fwd(K, n_dst, cin, cout);
-  return p.splits > 1 ? gpn::align_up((size_t)p.splits * n_dst * cout * sizeof(float)) : 0;
+  return gpn::spconv_fwd_route(K, n_dst, cin, cout).ws_bytes;
 }
 
 extern "C" int gpn_spconv_fwd_ordered(const float* in, const float* packed_w, const int32_t* nbr, const int32_t* nbr_p,
@@ -813,34 +828,6 @@ extern "C" int gpn_spconv_fwd_ordered(const float* in, const float* packed_w, co
 
 // out = conv (accumulate == 0) or out += conv (the network executor's second gradient of a slot: same value as staging the
 // conv's result and adding it with a separate launch, which is what it replaces)
-bool gpn::spconv_fwd_accumulates_stats(int K, int64_t n_dst, int cin, int cout) {
-  return n_dst > 0 && (gpn::spconv_tiles_supported(K, n_dst, cin, cout) || gpn::spconv_msplit_supported(K, n_dst, cin, cout) ||
-                       use_direct(K, n_dst, cin, cout));
-}
-
-// true if a conv of this shape runs on a kernel whose epilogue can apply a gpn::ConvAffine (an inference pass's BatchNorm): the
-// masked-tile and the masked tap-split kernel, and the direct kernel for k = 1
-bool gpn::spconv_fwd_applies_affine(int K, int64_t n_dst, int cin, int cout, const gpn::DevRows& rows) {
-  if (n_dst <= 0) return false;
-  const bool tiles = rows.dev ? (gpn::spconv_tiles_supported(K, n_dst, cin, cout) && gpn::spconv_tiles_supported(K, gpn::plan_rows(n_dst, rows), cin, cout))
-                              : gpn::spconv_tiles_supported(K, n_dst, cin, cout);
-  if (tiles || gpn::spconv_msplit_supported(K, n_dst, cin, cout)) return true;
-  return K == 1 && (rows.dev ? use_direct(K, std::max<int64_t>(n_dst, 256), cin, cout) : use_direct(K, n_dst, cin, cout));
-}
-
-// which kernel a layer takes when its row count is a device counter: decided from the host's plan (the layer must fit the
-// 32-bit offsets at its bound), never the lock-step kernel - that one sizes partial outputs from the row count
-static bool dev_rows_take_tiles(int K, int64_t n_bound, int64_t n_plan, int cin, int cout) {
-  return gpn::spconv_tiles_supported(K, n_bound, cin, cout) && gpn::spconv_tiles_supported(K, n_plan, cin, cout);
-}
-static bool dev_rows_take_direct(int K, int64_t n_bound, int cin, int cout) { return use_direct(K, std::max<int64_t>(n_bound, 256), cin, cout); }
-
-bool gpn::spconv_fwd_accumulates_stats(int K, int64_t n_dst, int cin, int cout, const gpn::DevRows& rows) {
-  if (!rows.dev) return gpn::spconv_fwd_accumulates_stats(K, n_dst, cin, cout);
-  return n_dst > 0 && (dev_rows_take_tiles(K, n_dst, gpn::plan_rows(n_dst, rows), cin, cout) ||
-                       gpn::spconv_msplit_supported(K, n_dst, cin, cout) || dev_rows_take_direct(K, n_dst, cin, cout));
-}
-
 int gpn::spconv_fwd_into(const float* in, const float* packed_w, const int32_t* nbr, const int32_t* nbr_p, const int32_t* perm,
                          int K, int64_t n_dst, int cin, int cout, float* out, int accumulate, const gpn::ConvStats& stats,
                          void* ws, size_t ws_bytes, hipStream_t stream, const gpn::DevRows& rows) {
@@ -850,30 +837,25 @@ int gpn::spconv_fwd_into(const float* in, const float* packed_w, const int32_t* 
   if (n_dst == 0) return GPN_OK;
   GPN_CHECK_ARG(in && packed_w && nbr && out);
   GPN_CHECK_ARG(!stats.twin.in || (stats.twin.packed && stats.twin.out && (stats.slab == nullptr) == (stats.twin.slab == nullptr)));
-  const int nt = cout / 16;
-  const int64_t n_plan = gpn::plan_rows(n_dst, rows);
-  const bool tiles = rows.dev ? dev_rows_take_tiles(K, n_dst, n_plan, cin, cout) : gpn::spconv_tiles_supported(K, n_dst, cin, cout);
-  if (tiles) {  // the masked-tile kernel (spconv_tiles.hip): every layer of >= 16 tiles
-    gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 0.0, 4.0 * (double)n_dst * cout, gpn::prof_shape_tag(K, n_dst, cin, cout, stats.twin.in != nullptr));
-    return gpn::spconv_tiles_launch(in, packed_w, nbr_p ? nbr_p : nbr, perm, K, n_dst, cin, cout, accumulate, stats, out, stream, rows);
-  }
-  if (gpn::spconv_msplit_supported(K, n_dst, cin, cout)) {  // the masked tap-split kernel (spconv_msplit.hip): every k = 27 / 8 layer below that
-    gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 0.0, 4.0 * (double)n_dst * cout, gpn::prof_shape_tag(K, n_dst, cin, cout, stats.twin.in != nullptr));
-    return gpn::spconv_msplit_launch(in, packed_w, nbr_p ? nbr_p : nbr, perm, K, n_dst, cin, cout, accumulate, stats, out, stream, rows);
-  }
-  if (rows.dev ? dev_rows_take_direct(K, n_dst, cin, cout) : use_direct(K, n_dst, cin, cout)) {
-    gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 0.0, 4.0 * (double)n_dst * cout, gpn::prof_shape_tag(K, n_dst, cin, cout, stats.twin.in != nullptr));
-    const int32_t* table = nbr_p ? nbr_p : nbr;
-    return K == 27 ? dispatch_direct<27>(in, packed_w, table, perm, n_dst, cin, nt, accumulate, stats, out, stream, rows)
-           : K == 8 ? dispatch_direct<8>(in, packed_w, table, perm, n_dst, cin, nt, accumulate, stats, out, stream, rows)
-                    : dispatch_direct<1>(in, packed_w, table, perm, n_dst, cin, nt, accumulate, stats, out, stream, rows);
-  }
-  if (rows.dev) {
-    gpn::set_error("gpn_spconv_fwd: a layer whose row count is a device counter must fit the masked-tile / direct kernels (K = %d, %d -> %d channels)", K, cin, cout);
-    return GPN_ERR_ARG;
+  const gpn::ConvRoute route = gpn::spconv_fwd_route(K, n_dst, cin, cout, rows);
+  const gpn::ConvCall c{in, packed_w, nbr_p ? nbr_p : nbr, perm, K, n_dst, cin, cout, accumulate, stats, out, stream, rows};
+  const int64_t tag = gpn::prof_shape_tag(K, n_dst, cin, cout, stats.twin.in != nullptr);
+  switch (route.kind) {
+    case gpn::ConvRoute::kTiles:
+    case gpn::ConvRoute::kMsplit:
+    case gpn::ConvRoute::kDirect: {
+      gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 0.0, 4.0 * (double)n_dst * cout, tag);
+      return route.kind == gpn::ConvRoute::kTiles    ? gpn::spconv_tiles_launch(c)
+             : route.kind == gpn::ConvRoute::kMsplit ? gpn::spconv_msplit_launch(c)
+                                                     : direct_launch(c);
+    }
+    case gpn::ConvRoute::kUnroutable:
+      gpn::set_error("gpn_spconv_fwd: a layer whose row count is a device counter must fit the masked-tile / direct kernels (K = %d, %d -> %d channels)", K, cin, cout);
+      return GPN_ERR_ARG;
+    default: break;  // the lock-step kernel, below
   }
   if (stats.slab || stats.twin.slab || stats.ep.mean) {
-    gpn::set_error("gpn_spconv_fwd: this shape runs on a kernel without a BatchNorm epilogue (see spconv_fwd_accumulates_stats / spconv_fwd_applies_affine)");
+    gpn::set_error("gpn_spconv_fwd: this shape runs on a kernel without a BatchNorm epilogue (see spconv_fwd_route)");
     return GPN_ERR_ARG;
   }
   if (stats.twin.in) {  // the lock-step kernel takes one problem per launch
@@ -883,30 +865,21 @@ int gpn::spconv_fwd_into(const float* in, const float* packed_w, const int32_t* 
     return gpn::spconv_fwd_into(tw.in, tw.packed, nbr, nbr_p, perm, K, n_dst, cin, cout, tw.out, accumulate, gpn::ConvStats(), ws, ws_bytes, stream);
   }
   const FwdPlan p = plan_fwd(K, n_dst, cin, cout);
-  float* target = out;
-  if (p.splits > 1) {
-    if (!ws || ws_bytes < (size_t)p.splits * n_dst * cout * sizeof(float)) {
-      gpn::set_error("gpn_spconv_fwd: workspace too small for %d tap splits", p.splits);
-      return GPN_ERR_WS;
-    }
-    target = static_cast<float*>(ws);
+  if (p.splits > 1 && (!ws || ws_bytes < (size_t)p.splits * n_dst * cout * sizeof(float))) {
+    gpn::set_error("gpn_spconv_fwd: workspace too small for %d tap splits", p.splits);
+    return GPN_ERR_WS;
   }
-  int rc;
-  {
-    gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 0.0, 4.0 * (double)n_dst * cout, gpn::prof_shape_tag(K, n_dst, cin, cout, stats.twin.in != nullptr));
-    switch (p.ntw) {
-      case 1: rc = dispatch_cw<1>(p, in, packed_w, nbr, K, n_dst, cin, nt, p.splits > 1 ? 0 : accumulate, target, stream); break;
-      case 2: rc = dispatch_cw<2>(p, in, packed_w, nbr, K, n_dst, cin, nt, p.splits > 1 ? 0 : accumulate, target, stream); break;
-      case 3: rc = dispatch_cw<3>(p, in, packed_w, nbr, K, n_dst, cin, nt, p.splits > 1 ? 0 : accumulate, target, stream); break;
-      default: rc = dispatch_cw<4>(p, in, packed_w, nbr, K, n_dst, cin, nt, p.splits > 1 ? 0 : accumulate, target, stream); break;
-    }
-    if (rc == GPN_OK && p.splits > 1) {
-      const int64_t elems4 = n_dst * cout / 4;
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)gpn::cdiv(elems4, 256)), dim3(256), 0, stream, target,
-                         p.splits, elems4, accumulate, out);
-      hipError_t e_ = hipGetLastError();
-      if (e_ != hipSuccess) { gpn::set_error("gpn_spconv_fwd: reduce launch failed: %s", hipGetErrorString(e_)); rc = GPN_ERR_HIP; }
-    }
+  // (the lock-step kernel reads the table in voxel order; tap splits write partial outputs that a fixed-order kernel sums)
+  float* target = p.splits > 1 ? static_cast<float*>(ws) : out;
+  const gpn::ConvCall lc{in, packed_w, nbr, nullptr, K, n_dst, cin, cout, p.splits > 1 ? 0 : accumulate, stats, target, stream, rows};
+  gpn::ProfScope prof(GPN_K_SPCONV_FWD, stream, 0.0, 4.0 * (double)n_dst * cout, tag);
+  int rc = launch_lockstep(p, lc);
+  if (rc == GPN_OK && p.splits > 1) {
+    const int64_t elems4 = n_dst * cout / 4;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)gpn::cdiv(elems4, 256)), dim3(256), 0, stream, target,
+                       p.splits, elems4, accumulate, out);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) { gpn::set_error("gpn_spconv_fwd: reduce launch failed: %s", hipGetErrorString(e_)); rc = GPN_ERR_HIP; }
   }
   return rc;
 }

@@ -33,11 +33,9 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
 #include "bn_stats.h"
-#include "gpn_common.h"
+#include "spconv_dispatch.h"
 
 namespace {
 
@@ -62,14 +60,7 @@ __device__ unsigned long long* g_msplit_trace = nullptr;  // [waves][10]
 #define GPN_MSPLIT_OPERAND_REGS 48
 #endif
 
-template <class F, int... I>
-__device__ __forceinline__ void ms_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>()), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void ms_static_for(F&& f) {
-  ms_static_for_impl(f, std::make_integer_sequence<int, N>());
-}
+using gpn::static_for;
 
 // taps in the ring: as many whole taps (CB stages of 1 + NT requests each) as the operand-register budget holds, at least one -
 // and at least three stages, so that a narrow layer still has requests in flight while a stage is in the MFMAs
@@ -277,7 +268,7 @@ __global__ __launch_bounds__(SP * 64) GPN_MSPLIT_OCC void spconv_msplit_kernel(c
       for (int nt = 0; nt < NT; ++nt) acc[nt] += part[nt];
     }
   };
-  ms_static_for<D - 1>([&](auto s) {
+  static_for<D - 1>([&](auto s) {
     issue_stage(s, std::integral_constant<int, decltype(s)::value % CB>());
   });
   __builtin_amdgcn_sched_barrier(0);
@@ -287,7 +278,7 @@ __global__ __launch_bounds__(SP * 64) GPN_MSPLIT_OCC void spconv_msplit_kernel(c
 #endif
   while (remaining >= ST) {
     remaining -= ST;
-    ms_static_for<D>([&](auto s) {
+    static_for<D>([&](auto s) {
       constexpr int sv = decltype(s)::value;
       issue_stage(std::integral_constant<int, (sv + D - 1) % D>(), std::integral_constant<int, (sv + D - 1) % CB>());
       __builtin_amdgcn_sched_barrier(0);
@@ -295,7 +286,7 @@ __global__ __launch_bounds__(SP * 64) GPN_MSPLIT_OCC void spconv_msplit_kernel(c
       __builtin_amdgcn_sched_barrier(0);
     });
   }
-  ms_static_for<D>([&](auto s) {  // the last remaining (< ST) taps: requested already
+  static_for<D>([&](auto s) {  // the last remaining (< ST) taps: requested already
     constexpr int sv = decltype(s)::value;
     if (sv / CB < remaining) consume_stage(s, std::integral_constant<int, sv % CB>());
   });
@@ -384,20 +375,10 @@ std::atomic<int> g_force_nt{0}, g_force_sp{0};
 // 6.7 at 489 rows x 96); the nine-wave form stays instantiated for the sweep
 std::atomic<int> g_sp9_from_nt{1 << 30};
 
-#define GPN_MSPLIT_CB(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(10) X(12) X(14)
-
-bool ms_width(int CB) {
-#define GPN_X(cb) if (CB == cb) return true;
-  GPN_MSPLIT_CB(GPN_X)
-#undef GPN_X
-  return false;
-}
-
 struct Cut {
   int nt, sp;
 };
-// the nine-wave form is instantiated where its ring fits the 168 registers a wave of a 576-thread workgroup can have
-constexpr bool ms_fits9(int CB, int NT) { return CB * (1 + NT) <= 28; }
+constexpr bool ms_fits9(int CB, int NT) { return CB * (1 + NT) <= gpn::kMsplitSp9MaxRegs4; }
 
 // Waves per row tile and column tiles per workgroup (tools/conv_msplit_sweep.py, profiles/r06_conv_msplit_sweep.txt).
 // SP fixes the summation grouping, so it must NOT depend on the row count: a device-counted launch (whose host only has a plan)
@@ -423,50 +404,42 @@ Cut pick_cut(int K, int64_t n_tiles, int CB, int nt_total) {
 }
 
 template <int CB, int NT, int SP>
-int launch_msplit(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                  int nt_total, int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream,
-                  const gpn::DevRows& rows) {
-  const int n_tiles = (int)gpn::cdiv(n_dst, 16);
+int launch_msplit(const gpn::ConvCall& c) {
+  const int nt_total = c.cout / 16;
+  const int n_tiles = (int)gpn::cdiv(c.n_dst, 16);
   const int col_groups = nt_total / NT;
   const int n_units = n_tiles * col_groups;
-  const int64_t plan_units = gpn::cdiv(gpn::plan_rows(n_dst, rows), 16) * col_groups;
-  const size_t packed_bytes = (size_t)K * CB * nt_total * 1024;
+  const int64_t plan_units = gpn::cdiv(gpn::plan_rows(c.n_dst, c.rows), 16) * col_groups;
+  const size_t packed_bytes = (size_t)c.K * CB * nt_total * 1024;
   // (an exactly-sized launch as FEWER workgroups that walk the units - 512 ... 1536 workgroups for the 1575 row tiles of the
   // 25k-row level, the device-counted form's loop: 29.3 - 35 us against 29.5, profiles/r06_conv_msplit_walk.txt - does not pay)
-  const dim3 grid(gpn::dev_grid(n_units, plan_units, rows.dev != nullptr, 8, 512), stats.twin.in ? 2 : 1);
-#define GPN_MS_LAUNCH(DEVV, EPV)                                                                                                      \
-  hipLaunchKernelGGL((spconv_msplit_kernel<CB, NT, SP, DEVV, EPV>), grid, dim3(SP * 64), 0, stream, in, packed, nbr, perm, K, n_dst, \
-                     n_tiles, n_units, nt_total, col_groups, packed_bytes, accumulate, stats, out, rows.dev)
-  if (stats.ep.mean) {  // (an inference pass: the BatchNorm behind the conv in the epilogue)
-    if (rows.dev) GPN_MS_LAUNCH(true, true);
-    else GPN_MS_LAUNCH(false, true);
-  } else {
-    if (rows.dev) GPN_MS_LAUNCH(true, false);
-    else GPN_MS_LAUNCH(false, false);
-  }
-#undef GPN_MS_LAUNCH
+  const dim3 grid(gpn::dev_grid(n_units, plan_units, c.rows.dev != nullptr, 8, 512), c.stats.twin.in ? 2 : 1);
+  // (EP: an inference pass, the BatchNorm behind the conv in the epilogue)
+  gpn::with_bools(c.rows.dev != nullptr, c.stats.ep.mean != nullptr, [&](auto dev, auto ep) {
+    hipLaunchKernelGGL((spconv_msplit_kernel<CB, NT, SP, decltype(dev)::value, decltype(ep)::value>), grid, dim3(SP * 64), 0, c.stream,
+                       c.in, c.packed, c.nbr, c.perm, c.K, c.n_dst, n_tiles, n_units, nt_total, col_groups, packed_bytes,
+                       c.accumulate, c.stats, c.out, c.rows.dev);
+  });
   GPN_CHECK_LAUNCH();
   return GPN_OK;
 }
 
 template <int CB, int NT>
-int dispatch_sp(int SP, const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                int nt_total, int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream, const gpn::DevRows& rows) {
-  if constexpr (ms_fits9(CB, NT)) {
-    if (SP == 9) return launch_msplit<CB, NT, 9>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-  }
-  return launch_msplit<CB, NT, 4>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
+int dispatch_sp(int SP, const gpn::ConvCall& c) {  // (pick_cut asks for nine waves only where that form is built)
+#define GPN_X(sp) \
+  if constexpr (sp != 9 || ms_fits9(CB, NT)) \
+    if (SP == sp) return launch_msplit<CB, NT, sp>(c);
+  GPN_MSPLIT_SP(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("masked tap-split", c);
 }
 
 template <int CB>
-int dispatch_nt(const Cut& c, const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                int nt_total, int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream, const gpn::DevRows& rows) {
-  switch (c.nt) {
-    case 1: return dispatch_sp<CB, 1>(c.sp, in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 2: return dispatch_sp<CB, 2>(c.sp, in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 3: return dispatch_sp<CB, 3>(c.sp, in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    default: return dispatch_sp<CB, 4>(c.sp, in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-  }
+int dispatch_nt(const Cut& cut, const gpn::ConvCall& c) {
+#define GPN_X(v) if (cut.nt == v) return dispatch_sp<CB, v>(cut.sp, c);
+  GPN_MSPLIT_NT(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("masked tap-split", c);
 }
 
 }  // namespace
@@ -476,22 +449,16 @@ namespace gpn {
 bool spconv_msplit_supported(int K, int64_t n_dst, int cin, int cout) {
   if (g_mode.load(std::memory_order_relaxed) == 0) return false;
   if (!(K == 27 || K == 8) || cin % 16 || cout % 16 || n_dst < 1) return false;
-  // 32-bit byte offsets: source rows (at most 8 n_dst of them, for a stride-2 conv), output rows, the neighbour table
-  if (n_dst * (int64_t)8 * std::max(cin, cout) * 4 >= ((int64_t)1 << 31) || (int64_t)K * n_dst * 4 >= ((int64_t)1 << 31)) return false;
-  return ms_width(cin / 16);
+  return conv_offsets_fit32(K, n_dst, cin, cout) && conv_width(cin / 16);
 }
 
-int spconv_msplit_launch(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                         int cin, int cout, int accumulate, const ConvStats& stats, float* out, hipStream_t stream,
-                         const DevRows& rows) {
-  const int CB = cin / 16, nt_total = cout / 16;
-  const Cut c = pick_cut(K, gpn::cdiv(gpn::plan_rows(n_dst, rows), 16), CB, nt_total);
-#define GPN_X(cb) \
-  if (CB == cb) return dispatch_nt<cb>(c, in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-  GPN_MSPLIT_CB(GPN_X)
+int spconv_msplit_launch(const ConvCall& c) {
+  const int CB = c.cin / 16;
+  const Cut cut = pick_cut(c.K, gpn::cdiv(gpn::plan_rows(c.n_dst, c.rows), 16), CB, c.cout / 16);
+#define GPN_X(cb) if (CB == cb) return dispatch_nt<cb>(cut, c);
+  GPN_CONV_CB(GPN_X)
 #undef GPN_X
-  gpn::set_error("gpn_spconv_fwd: no masked tap-split kernel for %d -> %d channels", cin, cout);
-  return GPN_ERR_ARG;
+  return conv_no_kernel("masked tap-split", c);
 }
 
 }  // namespace gpn

@@ -35,11 +35,9 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
 #include "bn_stats.h"
-#include "gpn_common.h"
+#include "spconv_dispatch.h"
 
 namespace {
 
@@ -81,14 +79,7 @@ __device__ __forceinline__ void split_bf16x3(const f32x4 a0, const f32x4 a1, bf1
 __device__ unsigned long long* g_tiles_trace = nullptr;  // [units][8]
 #endif
 
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>()), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {  // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
-  static_for_impl(f, std::make_integer_sequence<int, N>());
-}
+using gpn::static_for;
 
 constexpr int cfg_slots(int CB, int R, int NT) {  // operand slots of the tap loop's ring: what the register budget holds, 2 .. 6
   const int regs_per_tap = CB * (R + NT) * 4 + ((GPN_TILES_ABL & 16) ? (CB / 2) * NT * 4 : 0);
@@ -455,27 +446,21 @@ std::atomic<int64_t> g_min_tiles{4096};  // (gpn_spconv_tiles_min_tiles changes 
 constexpr int kMinWaves = 1536;  // a launch takes as many column tiles per wave as still leave this many waves
 
 template <int CB, int NT>
-int launch_tiles(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                 int nt_total, int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream,
-                 const gpn::DevRows& rows) {
-  constexpr int R = 1;
-  const int n_tiles = (int)gpn::cdiv(n_dst, 16);
+int launch_tiles(const gpn::ConvCall& c) {
+  constexpr int R = gpn::kTilesR;
+  const int nt_total = c.cout / 16;
+  const int n_tiles = (int)gpn::cdiv(c.n_dst, 16);
   const int col_groups = nt_total / NT;
   const int n_units = (int)gpn::cdiv(n_tiles, R) * col_groups;
-  const int64_t plan_units = gpn::cdiv(gpn::cdiv(gpn::plan_rows(n_dst, rows), 16), R) * col_groups;
-  const size_t packed_bytes = (size_t)K * CB * nt_total * 1024;
-  const dim3 grid(gpn::dev_grid(gpn::cdiv(n_units, 4), gpn::cdiv(plan_units, 4), rows.dev != nullptr, 8), stats.twin.in ? 2 : 1);
-#define GPN_TILES_LAUNCH(DEVV, EPV)                                                                                                   \
-  hipLaunchKernelGGL((spconv_tiles_kernel<CB, NT, R, DEVV, EPV>), grid, dim3(256), 0, stream, in, packed, nbr, perm, K, n_dst, n_tiles, \
-                     n_units, nt_total, col_groups, packed_bytes, accumulate, stats, out, rows.dev)
-  if (stats.ep.mean) {  // (an inference pass: the BatchNorm behind the conv in the epilogue)
-    if (rows.dev) GPN_TILES_LAUNCH(true, true);
-    else GPN_TILES_LAUNCH(false, true);
-  } else {
-    if (rows.dev) GPN_TILES_LAUNCH(true, false);
-    else GPN_TILES_LAUNCH(false, false);
-  }
-#undef GPN_TILES_LAUNCH
+  const int64_t plan_units = gpn::cdiv(gpn::cdiv(gpn::plan_rows(c.n_dst, c.rows), 16), R) * col_groups;
+  const size_t packed_bytes = (size_t)c.K * CB * nt_total * 1024;
+  const dim3 grid(gpn::dev_grid(gpn::cdiv(n_units, 4), gpn::cdiv(plan_units, 4), c.rows.dev != nullptr, 8), c.stats.twin.in ? 2 : 1);
+  // (EP: an inference pass, the BatchNorm behind the conv in the epilogue)
+  gpn::with_bools(c.rows.dev != nullptr, c.stats.ep.mean != nullptr, [&](auto dev, auto ep) {
+    hipLaunchKernelGGL((spconv_tiles_kernel<CB, NT, R, decltype(dev)::value, decltype(ep)::value>), grid, dim3(256), 0, c.stream, c.in,
+                       c.packed, c.nbr, c.perm, c.K, c.n_dst, n_tiles, n_units, nt_total, col_groups, packed_bytes, c.accumulate,
+                       c.stats, c.out, c.rows.dev);
+  });
   GPN_CHECK_LAUNCH();
   return GPN_OK;
 }
@@ -493,30 +478,12 @@ int cols_per_wave(int64_t n_tiles, int nt_total) {
   return (nt_total % 2 == 0 && n_tiles * (nt_total / 2) >= 512) ? 2 : 1;
 }
 
-// input widths (16-channel blocks) the kernel is instantiated for: those of a residual U-Net with channels 16 (l + 1),
-// l < 7, and of its decoder convs behind the skip concats (2c -> c)
-#define GPN_TILES_CB(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(10) X(12) X(14)
-
-bool supported_width(int CB) {
-#define GPN_X(cb) if (CB == cb) return true;
-  GPN_TILES_CB(GPN_X)
-#undef GPN_X
-  return false;
-}
-
 template <int CB>
-int dispatch_cols(int NT, const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                  int nt_total, int accumulate, const gpn::ConvStats& stats, float* out, hipStream_t stream,
-                  const gpn::DevRows& rows) {
-  switch (NT) {
-    case 1: return launch_tiles<CB, 1>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 2: return launch_tiles<CB, 2>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 3: return launch_tiles<CB, 3>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 4: return launch_tiles<CB, 4>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 5: return launch_tiles<CB, 5>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    case 6: return launch_tiles<CB, 6>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-    default: return launch_tiles<CB, 7>(in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-  }
+int dispatch_cols(int NT, const gpn::ConvCall& c) {
+#define GPN_X(nt) if (NT == nt) return launch_tiles<CB, nt>(c);
+  GPN_TILES_NT(GPN_X)
+#undef GPN_X
+  return gpn::conv_no_kernel("masked-tile", c);
 }
 
 }  // namespace
@@ -525,27 +492,22 @@ namespace gpn {
 
 bool spconv_tiles_supported(int K, int64_t n_dst, int cin, int cout) {
   if (!(K >= 1 && K <= kMaxTaps) || cin % 16 || cout % 16) return false;
-  // 32-bit byte offsets: source rows (at most 8 n_dst of them, for a stride-2 conv), output rows, the neighbour table
-  if (n_dst * (int64_t)8 * std::max(cin, cout) * 4 >= ((int64_t)1 << 31) || (int64_t)K * n_dst * 4 >= ((int64_t)1 << 31)) return false;
+  if (!conv_offsets_fit32(K, n_dst, cin, cout)) return false;
   // Below ~4096 tiles a launch has too few waves for the SIMDs to hide a wave's serial chain of (offset read, operand loads,
   // MFMAs) per tap behind other waves: in the training step (cold table, operands written by the previous kernel) the
   // direct kernel with its 4-stage operand ring and 10-tap index ring per wave is faster there (25k rows: 41 vs 48 us,
   // 1.8k rows: 22 vs 28 us; profiles/r03_conv_in_situ.txt), this kernel is at 80k / 144k rows (44 vs 60 us, 26 vs 28 us).
   if (gpn::cdiv(n_dst, 16) < std::max<int64_t>(g_min_tiles.load(std::memory_order_relaxed), 16)) return false;
-  return supported_width(cin / 16);
+  return conv_width(cin / 16);
 }
 
-int spconv_tiles_launch(const float* in, const float* packed, const int32_t* nbr, const int32_t* perm, int K, int64_t n_dst,
-                        int cin, int cout, int accumulate, const ConvStats& stats, float* out, hipStream_t stream,
-                        const DevRows& rows) {
-  const int CB = cin / 16, nt_total = cout / 16;
-  const int NT = cols_per_wave(gpn::cdiv(gpn::plan_rows(n_dst, rows), 16), nt_total);
-#define GPN_X(cb) \
-  if (CB == cb) return dispatch_cols<cb>(NT, in, packed, nbr, perm, K, n_dst, nt_total, accumulate, stats, out, stream, rows);
-  GPN_TILES_CB(GPN_X)
+int spconv_tiles_launch(const ConvCall& c) {
+  const int CB = c.cin / 16;
+  const int NT = cols_per_wave(gpn::cdiv(gpn::plan_rows(c.n_dst, c.rows), 16), c.cout / 16);
+#define GPN_X(cb) if (CB == cb) return dispatch_cols<cb>(NT, c);
+  GPN_CONV_CB(GPN_X)
 #undef GPN_X
-  gpn::set_error("gpn_spconv_fwd: no masked-tile kernel for %d -> %d channels", cin, cout);
-  return GPN_ERR_ARG;
+  return conv_no_kernel("masked-tile", c);
 }
 
 }  // namespace gpn

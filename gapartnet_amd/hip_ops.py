@@ -361,7 +361,8 @@ import os as _os
 # tile executes a tap as soon as ANY of its rows has that neighbour.  In voxel order a level-0 tile of the bench scenes runs
 # 4.3x the MFMA row-slots of its useful pairs, sorted by mask inside 16384-row blocks 2.1x (levels 1 / 2: 2.2x / 2.0x ->
 # 1.4x; stride-2 convs 4.4x -> 1.3x, inverse convs 4.3x -> 1.0x; tools/conv_tiles_bench.py).  The order costs a block-local sort (one workgroup per 16384 rows)
-# and a permuted table per rulebook; levels below 4096 tiles run on the direct kernel and keep voxel order.
+# and a permuted table per rulebook; levels below TILE_ORDER_MIN_ROWS rows keep voxel order (below 4096 tiles a level runs on
+# the masked tap-split kernel, which reads either order).
 # (round 4: also level 2 of the bench - 25k rows, direct / split kernel through `perm`: 8.17 / 8.23 / 8.14 -> 8.10 / 8.10 / 8.09 ms
 # per step in three interleaved same-box runs, profiles/r04_findings.md; 4096 gave nothing more)
 TILE_ORDER_MIN_ROWS = 16384  # (module attributes: tests and tools set them to order small inputs)

@@ -227,6 +227,13 @@ int gpn_rulebook_down_lists(const int32_t* fine_to_coarse, const int32_t* tap, i
 int gpn_spconv_pack_weights(const float* W, int K, int cin_w, int cout_w, int flags, float* packed,
                             gpn_stream_t stream);
 size_t gpn_spconv_fwd_ws_bytes(int K, int64_t n_dst, int cin, int cout);
+/* which kernel gpn_spconv_fwd* runs this shape on, under the current selection knobs (host arithmetic, no device needed).
+ * n_plan < 0: n_dst is the exact row count; n_plan >= 0: n_dst bounds a device-counted row count and n_plan is the host's
+ * estimate of it (0 = none).  Returns kind | sums << 8 | affine << 9: kind 0 = nothing to do (n_dst == 0), 1 = masked-tile,
+ * 2 = masked tap-split, 3 = direct (or its tap-split form), 4 = lock-step, 5 = no kernel takes it (GPN_ERR_ARG from the conv:
+ * a device-counted layer that fits none of 1 - 3, or K < 1 or a width below 16);
+ * sums / affine: that kernel's epilogue can accumulate BatchNorm column sums / apply an inference pass's BatchNorm. */
+int gpn_spconv_fwd_route(int K, int64_t n_dst, int64_t n_plan, int cin, int cout);
 int gpn_spconv_fwd(const float* in, const float* packed_w, const int32_t* nbr, int K, int64_t n_dst, int cin,
                    int cout, float* out, void* ws, size_t ws_bytes, gpn_stream_t stream);
 /* pack + conv in one call (packed copy lives in the head of ws); cin_w/cout_w are the STORED weight's dims */

@@ -217,11 +217,12 @@ def _src(name):
 
 
 def parsed_instantiations():
-    """{(CB, NT)} csrc/spconv_bf16.hip instantiates: GPN_BF16_CB x the column-tile counts of dispatch_cols"""
-    from tests.test_conv_instantiations import _body, _ints, _width_list
+    """{(CB, NT)} csrc/spconv_bf16.hip instantiates: the shared input-width list x the masked-tile column-tile counts"""
+    from tests.test_conv_instantiations import _width_list
     src = _src("spconv_bf16.hip")
-    nts = _ints(r"launch_bf16<CB, (\d+)>", _body(src, r"int dispatch_cols\("))
-    return {(cb, nt) for cb in _width_list(src, "GPN_BF16_CB") for nt in nts}
+    assert "GPN_CONV_CB(GPN_X)" in src and "GPN_TILES_NT(GPN_X)" in src
+    lists = _src("spconv_dispatch.h")
+    return {(cb, nt) for cb in _width_list(lists, "GPN_CONV_CB") for nt in _width_list(lists, "GPN_TILES_NT")}
 
 
 def test_every_bf16_instantiation_has_a_gpu_case():

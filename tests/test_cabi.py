@@ -26,7 +26,7 @@ def lib():
 
 def test_header_declares_the_hot_path():
     syms = declared_symbols()
-    for must in ("gpn_voxelize", "gpn_rulebook_subm3", "gpn_rulebook_down", "gpn_spconv_fwd", "gpn_spconv_wgrad",
+    for must in ("gpn_voxelize", "gpn_rulebook_subm3", "gpn_rulebook_down", "gpn_spconv_fwd", "gpn_spconv_fwd_route", "gpn_spconv_wgrad",
                  "gpn_ball_query", "gpn_ccl", "gpn_segmented_reduce", "gpn_segmented_maxpool_fwd", "gpn_instance_iou",
                  "gpn_nms", "gpn_pn2_furthest_point_sampling", "gpn_pn2_three_nn", "gpn_pn2_ball_query"):
         assert must in syms
@@ -79,6 +79,8 @@ def test_argument_errors_do_not_touch_the_device(lib):
 
 def test_workspace_queries_are_pure(lib):
     assert lib.gpn_voxelize_ws_bytes(ctypes.c_int64(20000), ctypes.c_int(6)) > 20000 * 8
+    # (the conv route: masked-tile with both epilogues at 80k rows; the whole rule in tests/test_conv_instantiations.py)
+    assert lib.gpn_spconv_fwd_route(ctypes.c_int(27), ctypes.c_int64(80000), ctypes.c_int64(-1), ctypes.c_int(32), ctypes.c_int(32)) == 0x301
     assert lib.gpn_rulebook_subm3_ws_bytes(ctypes.c_int64(1000)) > 27 * 1000 * 4
     assert lib.gpn_ccl_ws_bytes(ctypes.c_int64(1000)) >= 3 * 4000
 

@@ -1,7 +1,8 @@
 """CPU checks behind the conv instantiation sweep (tests/test_gpu_conv_shapes.py): the float64 reference of tests/conv_ref64.py
-pinned against torch's dense conv3d / conv_transpose3d, the profiler kernel-name parser, and a coverage check - every
-instantiation the conv sources build (parsed from their width lists and dispatch switches) is launched by some case of the GPU
-module's table, or listed in UNREACHABLE with the reason the dispatch cannot produce it.
+pinned against torch's dense conv3d / conv_transpose3d, the profiler kernel-name parser, a coverage check - every
+instantiation the conv sources build (the instantiation lists and constants of csrc/spconv_dispatch.h, which every dispatch
+expands) is launched by some case of the GPU module's table, or listed in UNREACHABLE with the reason the dispatch cannot produce
+it - and the library's routing decision (gpn_spconv_fwd_route) against the GPU module's restatement of it.
 
 The DEV (device-counted rows) and EP (an inference pass's BatchNorm in the epilogue) variants are outside this sweep; they run
 through the network executor in tests/test_gpu_model.py::test_inference_pass_applies_batchnorm_in_the_conv_epilogue,
@@ -120,19 +121,6 @@ def _src(name):
         return re.sub(r"//[^\n]*", "", fh.read())  # (comments dropped: they mention kernels and cases in prose)
 
 
-def _body(src, head):
-    """the brace-balanced body of the first function whose text starts with the regex ``head``"""
-    m = re.search(head, src)
-    assert m, f"no {head!r} in the source"
-    i = src.index("{", m.end())
-    depth = 0
-    for j in range(i, len(src)):
-        depth += {"{": 1, "}": -1}.get(src[j], 0)
-        if depth == 0:
-            return src[i:j + 1]
-    raise AssertionError(f"unbalanced body of {head!r}")
-
-
 def _ints(pattern, text):
     vals = sorted({int(v) for v in re.findall(pattern, text)})
     assert vals, f"nothing parsed by {pattern!r}: the source changed shape, update the parser"
@@ -145,52 +133,46 @@ def _width_list(src, macro):
     return _ints(r"X\((\d+)\)", m.group(1))
 
 
+def _const(src, name):
+    m = re.search(r"constexpr int " + name + r" = (\d+);", src)
+    assert m, f"no constant {name}"
+    return int(m.group(1))
+
+
 def parsed_instantiations():
-    """{(family, args)} the conv sources instantiate (DEV / EP = false)"""
+    """{(family, args)} the conv sources instantiate (DEV / EP = false): every dispatch of csrc/ is an expansion of a
+    ``#define NAME(X) X(..) X(..)`` list of csrc/spconv_dispatch.h, so the lists and its named constants are all that is read"""
+    src = _src("spconv_dispatch.h")
+    owners = {"GPN_CONV_CB": ("spconv_tiles.hip", "spconv_msplit.hip"), "GPN_TILES_NT": ("spconv_tiles.hip",),
+              "GPN_MSPLIT_NT": ("spconv_msplit.hip",), "GPN_MSPLIT_SP": ("spconv_msplit.hip",), "GPN_DIRECT_KT": ("spconv_fwd.hip",),
+              "GPN_DIRECT_CB": ("spconv_fwd.hip",), "GPN_SPLIT_WAYS": ("spconv_fwd.hip",), "GPN_LOCKSTEP_NTW": ("spconv_fwd.hip",),
+              "GPN_LOCKSTEP_CW": ("spconv_fwd.hip",), "GPN_LOCKSTEP_WAVES": ("spconv_fwd.hip",), "GPN_WGRAD_CT": ("spconv.hip",),
+              "GPN_WGRAD_NT": ("spconv.hip",)}
+
+    def lst(macro):  # (a list counts only if the dispatch of the file that owns the kernel expands it)
+        for fn in owners[macro]:
+            assert macro + "(GPN_X)" in _src(fn), f"{fn} does not expand {macro}"
+        return _width_list(src, macro)
+
     out = set()
-    # masked-tile: GPN_TILES_CB x the column-tile counts of dispatch_cols, R of launch_tiles
-    src = _src("spconv_tiles.hip")
-    R = _ints(r"constexpr int R = (\d+);", _body(src, r"int launch_tiles\("))
-    for cb in _width_list(src, "GPN_TILES_CB"):
-        for nt in _ints(r"launch_tiles<CB, (\d+)>", _body(src, r"int dispatch_cols\(")):
-            out.update(("tiles", (cb, nt, r, False, False)) for r in R)
-    # masked tap-split: GPN_MSPLIT_CB x dispatch_nt's NT x dispatch_sp's SP (SP 9 where ms_fits9)
-    src = _src("spconv_msplit.hip")
-    fit = re.search(r"ms_fits9\(int CB, int NT\) \{ return CB \* \(1 \+ NT\) <= (\d+); \}", src)
-    assert fit, "ms_fits9 changed shape"
-    sps = _ints(r"launch_msplit<CB, NT, (\d+)>", _body(src, r"int dispatch_sp\("))
-    for cb in _width_list(src, "GPN_MSPLIT_CB"):
-        for nt in _ints(r"dispatch_sp<CB, (\d+)>", _body(src, r"int dispatch_nt\(")):
-            for sp in sps:
-                if sp != 9 or cb * (1 + nt) <= int(fit.group(1)):
-                    out.add(("msplit", (cb, nt, sp, False, False)))
-    # direct kernel (KT from spconv_fwd_into's dispatch_direct<KT>, CB from dispatch_direct) and its tap-split forms (KT >= 8)
-    src = _src("spconv_fwd.hip")
-    fwd_into = _body(src, r"int gpn::spconv_fwd_into\(")
-    kts = _ints(r"dispatch_direct<(\d+)>", fwd_into)
-    cbs = _ints(r"launch_direct<KT, (\d+)>", _body(src, r"int dispatch_direct\("))
-    ld = _body(src, r"int launch_direct\(")
-    split_from = int(re.search(r"if constexpr \(KT >= (\d+)\)", ld).group(1))
-    ways = _ints(r"launch_split<KT, CB, (\d+)>", ld)
-    for kt in kts:
-        for cb in cbs:
+    # masked-tile: input widths x column tiles per wave, R row tiles per wave
+    out.update(("tiles", (cb, nt, _const(src, "kTilesR"), False, False)) for cb in lst("GPN_CONV_CB") for nt in lst("GPN_TILES_NT"))
+    # masked tap-split: input widths x column tiles per workgroup x waves per row tile (nine where the ring fits)
+    fit9 = _const(src, "kMsplitSp9MaxRegs4")
+    out.update(("msplit", (cb, nt, sp, False, False)) for cb in lst("GPN_CONV_CB") for nt in lst("GPN_MSPLIT_NT")
+               for sp in lst("GPN_MSPLIT_SP") if sp != 9 or cb * (1 + nt) <= fit9)
+    # direct kernel and its tap-split forms (layers of at least kSplitMinTaps taps)
+    for kt in lst("GPN_DIRECT_KT"):
+        for cb in lst("GPN_DIRECT_CB"):
             out.add(("direct", (kt, cb, False, False)))
-            if kt >= split_from:
-                out.update(("split", (kt, cb, w, False)) for w in ways)
-    # lock-step: NTW from spconv_fwd_into's switch, CW from dispatch_cw, NS = ceil(CW NTW / waves) for dispatch_ns's wave counts
-    ntws = _ints(r"dispatch_cw<(\d+)>", fwd_into)
-    cws = _ints(r"dispatch_ns<NTW, (\d+)>", _body(src, r"int dispatch_cw\("))
-    waves = _ints(r"\(X \+ \d+\) / (\d+)", _body(src, r"int dispatch_ns\("))
-    for ntw in ntws:
-        for cw in cws:
-            out.update(("lockstep", (ntw, cw, -(-(cw * ntw) // w))) for w in waves)
-    if "reduce_partials_kernel" in fwd_into:
+            if kt >= _const(src, "kSplitMinTaps"):
+                out.update(("split", (kt, cb, w, False)) for w in lst("GPN_SPLIT_WAYS"))
+    # lock-step: NS = ceil(CW NTW / waves per workgroup); its tap splits are summed by the reduce kernel
+    out.update(("lockstep", (ntw, cw, -(-(cw * ntw) // w))) for ntw in lst("GPN_LOCKSTEP_NTW") for cw in lst("GPN_LOCKSTEP_CW")
+               for w in lst("GPN_LOCKSTEP_WAVES"))
+    if "reduce_partials_kernel" in _src("spconv_fwd.hip"):
         out.add(("reduce", ()))
-    # weight gradient: wgrad_contract's CT switch x dispatch_wgrad_nt's cases
-    src = _src("spconv.hip")
-    cts = _ints(r"dispatch_wgrad_nt<(\d+)>", _body(src, r"int wgrad_contract\("))
-    nts = _ints(r"GPN_CASE\((\d+)\)", _body(src, r"int dispatch_wgrad_nt\("))
-    out.update(("wgrad", (ct, nt)) for ct in cts for nt in nts)
+    out.update(("wgrad", (ct, nt)) for ct in lst("GPN_WGRAD_CT") for nt in lst("GPN_WGRAD_NT"))
     return out
 
 
@@ -223,3 +205,77 @@ def test_case_table_is_well_formed():
     assert n_max * 8 * 16 * 4 < 2 ** 31 <= (n_max + 1) * 8 * 16 * 4
     assert T.route(27, n_max, 16, 16)[0][0] == "tiles" and T.route(27, n_max + 1, 16, 16)[0][0] == "lockstep"
     assert math.isclose(n_max, 4194303)
+
+
+# ---------------------------------------------------------------------------------------------------- routing
+KIND = {"tiles": 1, "msplit": 2, "direct": 3, "split": 3, "lockstep": 4}
+UNROUTABLE = 5
+
+
+def _flags(kind, K):
+    """the rule of gpn::ConvRoute: which kinds have BatchNorm sums / an inference BatchNorm in their epilogue"""
+    return kind | (kind in (1, 2, 3)) << 8 | (kind in (1, 2) or (kind == 3 and K == 1)) << 9
+
+
+def test_library_route_equals_the_restated_route():
+    """gpn_spconv_fwd_route (what spconv_fwd_into launches by and the executor plans by) against the independent restatement of
+    tests/test_gpu_conv_shapes.py, at and either side of every threshold and under every knob setting of the case table; the
+    device-counted rule (a kernel must fit at the bound AND, for the masked-tile kernel, at the plan) restated here."""
+    import ctypes
+    from gapartnet_amd import _C
+    from tests import test_gpu_conv_shapes as T
+    if not os.path.exists(_C.SO_PATH):
+        _C.build()
+    L = _C.lib()
+    L.gpn_spconv_fwd_route.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+    L.gpn_spconv_fwd_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+    n_guard = next(c.n for c in T.CASES if c.id == "guard-below")
+    knobs = (T.DEFAULT, T.LOW, T.NO_TILES, T.MS_OFF, T._direct(1), T._direct(2), T._direct(4), T.Knobs(ms=(0, 0, 0)))
+
+    def tiles_ok(K, n, cin, cout, kn):
+        return 1 <= K <= 27 and T._fits32(K, n, cin, cout) and T.cdiv(n, 16) >= max(kn.min_tiles, 16) and cin // 16 in T.TILES_CB
+
+    def route_dev(K, bound, plan, cin, cout, kn):
+        p = min(plan, bound) if plan > 0 else bound
+        fits = T._fits32(K, bound, cin, cout)
+        if tiles_ok(K, bound, cin, cout, kn) and tiles_ok(K, p, cin, cout, kn):
+            return 1
+        if kn.ms[0] and K in (27, 8) and fits and cin // 16 in T.MSPLIT_CB:
+            return 2
+        if K in (27, 8, 1) and cin // 16 in T.DIRECT_CB and T._fits32(K, max(bound, 256), cin, cout):
+            return 3  # (max(bound, 256) rows are 16 row tiles: the direct kernel's size floor never refuses)
+        return UNROUTABLE
+
+    try:
+        for kn in knobs:
+            T._knobs(L, kn)
+            for K in (1, 2, 8, 27):
+                for cb in range(1, 17):
+                    for cout in (16, 64, 224, 256):
+                        cin = 16 * cb
+                        n_fit = (1 << 31) // (8 * max(cin, cout) * 4)  # the first row count past the 32-bit offsets
+                        for n in (1, 15, 240, 255, 256, 257, 16 * 4095, 16 * 4096 - 1, 16 * 4096, 16 * 4096 + 1, n_fit - 1, n_fit, n_guard,
+                                  n_guard + 1):
+                            fam = T.route(K, n, cin, cout, kn)[0][0]
+                            got = L.gpn_spconv_fwd_route(K, n, -1, cin, cout)
+                            assert got == _flags(KIND[fam], K), (kn, K, n, cin, cout, fam, got)
+                            if tiles_ok(K, n, cin, cout, kn):
+                                assert fam == "tiles"
+                            ws = L.gpn_spconv_fwd_ws_bytes(K, n, cin, cout)
+                            splits = T.plan_fwd(K, n, cin, cout)[3]
+                            want = -(-splits * n * cout * 4 // 256) * 256 if fam == "lockstep" and splits > 1 else 0
+                            assert ws == want, (kn, K, n, cin, cout, fam, ws, want)
+                        # device-counted rows: bounds and plans on both sides of the 16-tile and the 4096-tile threshold
+                        for bound in (200, 257, 16 * 4096 - 1, 16 * 4096 + 1, n_fit) if cout in (16, 256) else ():
+                            for plan in (0, 240, 255, 257, 16 * 4095, 16 * 4096 - 1, 16 * 4096 + 1, bound + 5):
+                                want = route_dev(K, bound, plan, cin, cout, kn)
+                                got = L.gpn_spconv_fwd_route(K, bound, plan, cin, cout)
+                                assert got == _flags(want, K), (kn, K, bound, plan, cin, cout, want, got)
+            assert L.gpn_spconv_fwd_route(27, 0, -1, 16, 16) == 0 and L.gpn_spconv_fwd_route(27, 0, 0, 16, 16) == 0
+        # a bound above the masked-tile kernel's size and a plan below it must not take that kernel
+        for kn, bound, plan, want in ((T.DEFAULT, 70000, 60000, 2), (T.Knobs(ms=(0, 0, 0)), 70000, 60000, 3), (T.LOW, 300, 200, 2),
+                                      (T.DEFAULT, 70000, 70000, 1), (T.DEFAULT, 70000, 0, 1), (T.LOW, 300, 260, 1)):
+            T._knobs(L, kn)
+            assert L.gpn_spconv_fwd_route(27, bound, plan, 32, 32) & 0xff == want, (kn, bound, plan)
+    finally:
+        T._knobs(L, T.DEFAULT)

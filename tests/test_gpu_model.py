@@ -380,7 +380,7 @@ def test_conv_epilogue_batchnorm_sums_are_deterministic_and_used(cuda):
     reduces = sum(e.count for e in prof.key_averages() if "bn_reduce_kernel" in e.key)
     applies = sum(e.count for e in prof.key_averages() if "bn_apply_fwd_fold_kernel" in e.key)
     assert applies > 0, names
-    # only BatchNorms behind a k = 1 conv (lock-step kernel, no sum epilogue) keep their statistics launches
+    # only BatchNorms behind a conv on the lock-step kernel (no sum epilogue) keep their statistics launches
     assert reduces <= applies, (reduces, applies, names)
 
 

@@ -2,8 +2,9 @@
 (events around back-to-back launches with packed weights and prebuilt rulebooks - no wrapper, no packing in the timed region),
 useful TFLOP/s (2 P Cin Cout) against the fp32 MFMA peak, and how many MFMA row-slots a launch executes per useful pair.
 
-  python tools/conv_tiles_bench.py            # masked-tile kernel, tile order on for >= GPN_TILE_ORDER_MIN_ROWS rows
-  GPN_CONV_TILES=0 python tools/conv_tiles_bench.py   # the round-2 direct kernel on the same inputs
+  python tools/conv_tiles_bench.py             # masked-tile kernel, tile order on for >= hip_ops.TILE_ORDER_MIN_ROWS rows
+  python tools/conv_tiles_bench.py --no-tiles  # the same inputs with the masked-tile kernel kept away (gpn_spconv_tiles_min_tiles):
+                                               # the masked tap-split / direct kernels take every level
 
 Every (level, channels) case also checks the output against the plain-table launch of the same kernel (bit-equal) and, in the
 default mode, prints the largest difference to the other kernel's summation order when GPN_CONV_REF=path holds its outputs."""
@@ -23,6 +24,7 @@ MFMA_PEAK = 157.3
 if os.environ.get("GPN_PROBE_SO"):  # a measurement build of the library (tools/probes/tiles_ablation.sh)
     _C.SO_PATH = os.path.abspath(os.environ["GPN_PROBE_SO"])
 L = _C.lib()
+NO_TILES = "--no-tiles" in sys.argv[1:]
 
 
 def timeit(fn, iters=int(os.environ.get('BENCH_ITERS', 40)), warm=int(os.environ.get('BENCH_WARM', 5))):
@@ -78,7 +80,9 @@ def main():
     pcs = [pc.to(dev) for pc in make_batch(8, 20000)]
     batch = PointCloud.collate(pcs, voxel_size=(0.01, 0.01, 0.01))
     idx, shape = batch.voxel_tensor.indices, list(batch.voxel_tensor.spatial_shape)
-    print(f"# GPN_CONV_TILES={os.environ.get('GPN_CONV_TILES', '1')} tile order from {H.TILE_ORDER_MIN_ROWS} rows, "
+    if NO_TILES:
+        L.gpn_spconv_tiles_min_tiles(1 << 40)
+    print(f"# masked-tile kernel {'off' if NO_TILES else 'on'}, tile order from {H.TILE_ORDER_MIN_ROWS} rows, "
           f"blocks of {H.TILE_ORDER_BLOCK}")
     print(f"{'level rows':>14s} {'pairs/row':>9s} {'conv':>9s} {'us':>8s} {'TF':>7s} {'/mfma':>6s} {'slots/pair R1':>13s} {'R2':>6s}")
     ref_path = os.environ.get("GPN_CONV_REF")
