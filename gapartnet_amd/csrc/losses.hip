@@ -168,7 +168,9 @@ __global__ __launch_bounds__(kThreads) void point_losses_bwd_kernel(
       card += p[c] + y;
     }
   }
-  const float dice_scale = g_dice * (-2.0f / (card + 1e-8f));
+  // (a row without a class has y_c = 1e-6 for every c: I = 1e-6 sum_c p_c, so y_c - I is zero but for the rounding of the
+  // softmax's sum - such a row, an ignored one above all, gets an exact zero instead of that noise)
+  const float dice_scale = has_class ? g_dice * (-2.0f / (card + 1e-8f)) : 0.f;
 #pragma unroll
   for (int c = 0; c < kMaxClasses; ++c) {
     if (c < C) {
