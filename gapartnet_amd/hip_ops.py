@@ -1595,20 +1595,39 @@ def cloud_prepare(points, offsets, m, max_groups=0):
     nb = max(max((b - a for a, b in zip(host[:-1], host[1:])), default=1), 1)
     packed = torch.empty((S, nb, 4), dtype=torch.float32, device=dev)
     rows = torch.empty((S, nb), dtype=torch.int32, device=dev)
-    # counts, status and scale share one buffer: one copy to the host
-    tail = torch.zeros((S, 6), dtype=torch.float64, device=dev)
-    ints = tail[:, 4:].view(torch.int32)  # [S, 4] i32: column 0 counts, column 1 status
     counts, status = torch.empty((S,), dtype=torch.int32, device=dev), torch.empty((S,), dtype=torch.int32, device=dev)
+    if S > 0:
+        check(_C.lib().gpn_cloud_pack(ptr(points), i64(M), i32(pitch), ptr(off_dev), i32(S), i64(nb), ptr(packed), ptr(rows),
+                                      ptr(counts), ptr(status), _stream()), "gpn_cloud_pack")
+    return _sample_and_finish(points, pitch, off_dev, S, packed, rows, nb, counts, status, m, max_groups)
+
+
+def cloud_finish(points, pitch, off_dev, rows, n_bound, counts, idx, status, m):
+    """gpn_cloud_finish: points [M, C] f32 of row pitch ``pitch``, off_dev [S+1] i64, rows [S, n_bound] i32 (the valid rows of
+    every cloud), counts / status [S] i32, idx [S, m] i32 (gpn_view_fps) -> (out [S, m, C] f32, sample_rows [S, m] i32,
+    scale [S, 4] f64) on the device; status is updated in place"""
+    dev = points.device
+    S, C = int(counts.shape[0]), int(points.shape[1])
     out = torch.empty((S, m, C), dtype=torch.float32, device=dev)
     sample_rows = torch.empty((S, m), dtype=torch.int32, device=dev)
     scale = torch.empty((S, 4), dtype=torch.float64, device=dev)
-    L = _C.lib()
     if S > 0:
-        check(L.gpn_cloud_pack(ptr(points), i64(M), i32(pitch), ptr(off_dev), i32(S), i64(nb), ptr(packed), ptr(rows), ptr(counts),
-                               ptr(status), _stream()), "gpn_cloud_pack")
-        idx = view_fps(packed, counts, status, m, max_groups)
-        check(L.gpn_cloud_finish(ptr(points), i64(M), i32(pitch), i32(C), ptr(off_dev), i32(S), i64(nb), ptr(rows), ptr(counts), ptr(idx),
-                                 i32(m), ptr(status), ptr(out), ptr(sample_rows), ptr(scale), _stream()), "gpn_cloud_finish")
+        check(_C.lib().gpn_cloud_finish(ptr(points), i64(points.shape[0]), i32(pitch), i32(C), ptr(off_dev), i32(S), i64(n_bound),
+                                        ptr(rows), ptr(counts), ptr(idx), i32(m), ptr(status), ptr(out), ptr(sample_rows), ptr(scale),
+                                        _stream()), "gpn_cloud_finish")
+    return out, sample_rows, scale
+
+
+def _sample_and_finish(points, pitch, off_dev, S, packed, rows, n_bound, counts, status, m, max_groups):
+    """what follows the packing, for raw clouds (cloud_prepare) and frames (frame_prepare) alike: gpn_view_fps over ``packed``,
+    gpn_cloud_finish over ``rows`` [S, n_bound], then counts, status and scale in ONE copy to the host"""
+    dev = points.device
+    # counts, status and scale share one buffer: one copy to the host
+    tail = torch.zeros((S, 6), dtype=torch.float64, device=dev)
+    ints = tail[:, 4:].view(torch.int32)  # [S, 4] i32: column 0 counts, column 1 status
+    idx = view_fps(packed, counts, status, m, max_groups) if S > 0 else None
+    out, sample_rows, scale = cloud_finish(points, pitch, off_dev, rows, n_bound, counts, idx, status, m)
+    if S > 0:
         tail[:, :4] = scale
         ints[:, 0] = counts
         ints[:, 1] = status
@@ -1640,6 +1659,74 @@ def cloud_nearest(points, offsets, sample_rows, counts, status, want_d2=False):
     else:
         nn.fill_(-1)
     return (nn, d2) if want_d2 else nn
+
+
+# ---------------------------------------------------------------------------------------------------- FR (RGB-D frames)
+_FRAME_DEPTH = {torch.float32: 0, torch.float64: 1, torch.uint16: 2, torch.int16: 2}
+
+
+def frame_backproject(depth, rgb, K, keep=None, depth_scale=1.0, flip=False):
+    """depth [V,H,W] f32 / f64 / u16 (int16 storage is read as u16), rgb [V,H,W,3] u8, K [V,3,3] f64, keep [V,H,W] u8 / bool or None
+    -> (rows [V*H*W, 6] f32 with NaN xyz on invalid pixels, valid [V,H,W] u8, valid_counts [V] i32), all on the device
+    (include/gpn.h section FR)"""
+    dev = _dev(depth, rgb, K)
+    if depth.dtype not in _FRAME_DEPTH or depth.dim() != 3:
+        raise _C.GpnError(f"frame depth must be [V,H,W] float32, float64 or uint16, got {depth.dtype} {tuple(depth.shape)}")
+    V, H, W = (int(v) for v in depth.shape)
+    depth = depth.contiguous()
+    rgb, K = _c(rgb, torch.uint8), _c(K, torch.float64)
+    if tuple(rgb.shape) != (V, H, W, 3) or K.numel() != V * 9:
+        raise _C.GpnError("frame_backproject: rgb must be [V,H,W,3] and K [V,3,3]")
+    if keep is not None:
+        _dev(keep)
+        keep = _c(keep.to(torch.uint8) if keep.dtype == torch.bool else keep, torch.uint8)
+        if tuple(keep.shape) != (V, H, W):
+            raise _C.GpnError("frame_backproject: keep must be [V,H,W]")
+    rows = torch.empty((V * H * W, 6), dtype=torch.float32, device=dev)
+    valid = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    valid_counts = torch.empty((V,), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_frame_backproject(ptr(depth), i32(_FRAME_DEPTH[depth.dtype]), _C.ctypes.c_double(float(depth_scale)), ptr(rgb),
+                                         ptr(keep), ptr(K), i32(V), i32(H), i32(W), i32(1 if flip else 0), ptr(rows), ptr(valid),
+                                         ptr(valid_counts), _stream()), "gpn_frame_backproject")
+    return rows, valid, valid_counts
+
+
+def frame_select(rows, valid, valid_counts, seeds, cap, hash_bits=32):
+    """the seeded presample and the ordered compaction of section FR: rows [V*H*W, 6] f32, valid [V,H,W] u8, valid_counts [V] i32,
+    seeds [V] (uint32 values) -> (packed [V, n_bound, 4] f32, pix [V, H*W] i32 = the kept pixels ascending, counts [V] i32,
+    status [V] i32); n_bound = cap, or H*W for cap == 0 (no presample)"""
+    dev = _dev(rows, valid, valid_counts)
+    V, H, W = (int(v) for v in valid.shape)
+    cap = int(cap)
+    nb = cap if cap > 0 else H * W
+    seeds = torch.as_tensor(np.asarray(seeds, dtype=np.int64).astype(np.uint32).view(np.int32).reshape(-1)).to(dev, non_blocking=True)
+    if seeds.shape[0] != V or rows.shape[0] != V * H * W:
+        raise _C.GpnError("frame_select: one seed per frame and one row per pixel")
+    packed = torch.empty((V, nb, 4), dtype=torch.float32, device=dev)
+    pix = torch.empty((V, H * W), dtype=torch.int32, device=dev)
+    counts = torch.empty((V,), dtype=torch.int32, device=dev)
+    status = torch.empty((V,), dtype=torch.int32, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_frame_select_ws_bytes(i32(V), i32(H), i32(W)), dev)
+    check(L.gpn_frame_select(ptr(rows), ptr(valid), ptr(valid_counts), ptr(seeds), i32(V), i32(H), i32(W), i32(cap), i32(hash_bits),
+                             i64(nb), ptr(packed), ptr(pix), ptr(counts), ptr(status), ptr(ws), szt(ws.numel()), _stream()),
+          "gpn_frame_select")
+    return packed, pix, counts, status
+
+
+def frame_prepare(depth, rgb, K, m, cap, seeds, keep=None, depth_scale=1.0, flip=False, hash_bits=32, max_groups=0):
+    """V RGB-D frames of one size -> the network's input (include/gpn.h sections FR and CP): gpn_frame_backproject,
+    gpn_frame_select, gpn_view_fps over at most ``cap`` rows a frame, gpn_cloud_finish; no host read between them and ONE at the
+    end (counts, status, scale).  -> what cloud_prepare returns (a frame is the cloud of its H*W pixel rows; sample_rows are pixel
+    indices), plus ``rows`` [V*H*W, 6] f32 and ``valid_counts`` [V] i32 on the device."""
+    V, H, W = (int(v) for v in depth.shape)
+    rows, valid, valid_counts = frame_backproject(depth, rgb, K, keep, depth_scale, flip)
+    packed, pix, counts, status = frame_select(rows, valid, valid_counts, seeds, cap, hash_bits)
+    off_dev = torch.tensor([v * H * W for v in range(V + 1)], dtype=torch.int64).to(rows.device, non_blocking=True)
+    # (pix has the pitch H*W: gpn_cloud_finish bounds the row indices it reads by its n_bound)
+    got = _sample_and_finish(rows, 6, off_dev, V, packed, pix, H * W, counts, status, int(m), max_groups)
+    got.update(rows=rows, valid_counts=valid_counts)
+    return got
 
 
 # ---------------------------------------------------------------------------------------------------- VS (test-time rendering)

@@ -12,6 +12,12 @@ end tools/visu_utils.py:141-173 ``OBJfile2points`` / ``FindMaxDis`` / ``WorldSpa
 ``python -m gapartnet_amd.inference --ckpt X --input a.npy b.obj ... --out DIR [--num_points N] [--inference_dtype bf16]
         [--panels] [--no_flip] [--masks a.npz b.npz ...]``   (``--masks``: parallel to ``--input``, each file ``masks`` [K, N] and
         ``labels`` [K]; the output gains the ``mask_*`` arrays and the panels draw the masks' boxes)
+``prepare_frames`` / ``PartPredictor.predict_frames`` / ``predict_frames_with_masks``  the same from RGB-D frames: depth, image and
+                     intrinsics in (the reference's ObjIns.get_pc / get_downsampled_pc), per-pixel parts, camera-frame boxes and the
+                     image with the boxes drawn out (csrc/frameprep.hip; include/gpn.h section FR)
+``python -m gapartnet_amd.inference --ckpt X --depth d.npy|d.png --rgb i.png --intrinsics K.txt|K.npy [--depth_scale 1000
+        --keep_mask m.png --flip --presample 4 --seed 0 --masks a.npz] --out DIR``   writes DIR/<name>.npz and DIR/<name>_overlay.png
+        (``--masks``: ``masks`` [K, H, W] and ``labels`` [K] per frame); frames of different sizes go in separate batches
 
 CUDA tensors run on the HIP library; CPU tensors take the same graph in torch ops (FPS as a plain loop) - for tests and tiny
 inputs, never chosen for a CUDA tensor.
@@ -174,6 +180,232 @@ def nearest_samples(prep: PreparedClouds) -> torch.Tensor:
     return torch.cat(out)
 
 
+# ---------------------------------------------------------------------------------------------------- RGB-D frames
+def frame_hash(seed: int, pixel: np.ndarray, hash_bits: int = 32) -> np.ndarray:
+    """the presample's hash (include/gpn.h section FR), uint32: mix(mix(pixel + seed * 0x9E3779B9) ^ seed) >> (32 - hash_bits)"""
+    def mix(x):
+        x = x ^ (x >> np.uint32(16))
+        x = x * np.uint32(0x7feb352d)
+        x = x ^ (x >> np.uint32(15))
+        x = x * np.uint32(0x846ca68b)
+        return x ^ (x >> np.uint32(16))
+
+    seed = np.uint32(int(seed) & 0xffffffff)
+    with np.errstate(over="ignore"):
+        h = mix(mix(np.asarray(pixel).astype(np.uint32) + seed * np.uint32(0x9E3779B9)) ^ seed)
+    return h >> np.uint32(32 - int(hash_bits))
+
+
+def select_pixels(valid_pixels: np.ndarray, seed: int, cap: int, hash_bits: int = 32) -> np.ndarray:
+    """the seeded presample on the host: of the valid pixels (linear indices) the ``cap`` with the smallest key
+    (hash << 32) | pixel, ascending; all of them when there are at most ``cap`` or ``cap`` is 0"""
+    pix = np.sort(np.asarray(valid_pixels, dtype=np.int64))
+    if cap <= 0 or pix.shape[0] <= cap:
+        return pix
+    key = (frame_hash(seed, pix, hash_bits).astype(np.uint64) << np.uint64(32)) | pix.astype(np.uint64)
+    return np.sort(pix[np.argsort(key, kind="stable")[:cap]])
+
+
+def _frame_seeds(seed, V: int) -> List[int]:
+    """one uint32 per frame: a sequence as given, an int s as s, s + 1, ... (mod 2^32)"""
+    if isinstance(seed, (int, np.integer)):
+        return [(int(seed) + v) & 0xffffffff for v in range(V)]
+    seeds = [int(s) & 0xffffffff for s in (seed.tolist() if hasattr(seed, "tolist") else seed)]
+    if len(seeds) != V:
+        raise ValueError(f"{V} frames need {V} seeds, got {len(seeds)}")
+    return seeds
+
+
+def _backproject_numpy(depth, rgb, K, keep, depth_scale, flip):
+    """section FR's back-projection on host arrays -> (rows [V*H*W, 6] f32, valid [V, H*W] bool)"""
+    V, H, W = depth.shape
+    with np.errstate(all="ignore"):
+        z = depth.astype(np.float64) / np.float64(depth_scale)
+        valid = np.isfinite(z) & (z > 0)
+        if keep is not None:
+            valid &= np.asarray(keep).reshape(V, H, W) != 0
+        u = np.arange(W, dtype=np.float64)[None, None, :]
+        v = np.arange(H, dtype=np.float64)[None, :, None]
+        Kd = np.asarray(K, dtype=np.float64).reshape(V, 3, 3)
+        x = ((u - Kd[:, 0, 2, None, None]) * z) / Kd[:, 0, 0, None, None]
+        y = ((v - Kd[:, 1, 2, None, None]) * z) / Kd[:, 1, 1, None, None]
+        xyz = np.stack([x, y, z], -1).astype(np.float32)
+    valid &= np.isfinite(xyz).all(-1)
+    if flip:
+        xyz[..., 1:] = -xyz[..., 1:]
+    xyz[~valid] = np.nan
+    col = (np.asarray(rgb).reshape(V, H, W, 3).astype(np.float64) / 255.0).astype(np.float32)
+    return np.concatenate([xyz, col], -1).reshape(V * H * W, 6), valid.reshape(V, H * W)
+
+
+def _check_frames(depth, rgb, K, keep):
+    depth, rgb = torch.as_tensor(depth), torch.as_tensor(rgb)
+    if depth.dim() == 2:
+        depth, rgb = depth[None], rgb[None]
+    if depth.dim() != 3 or depth.dtype not in (torch.float32, torch.float64, torch.uint16, torch.int16):
+        raise ValueError("depth must be [V, H, W] (or [H, W]) float32, float64 or uint16")
+    V, H, W = (int(v) for v in depth.shape)
+    if tuple(rgb.shape) != (V, H, W, 3) or rgb.dtype != torch.uint8:
+        raise ValueError(f"rgb must be uint8 [{V}, {H}, {W}, 3]")
+    K = torch.as_tensor(K).detach().cpu().double()  # (host data: the overlay's camera is read from it)
+    if K.numel() == 9:
+        K = K.reshape(1, 3, 3).expand(V, 3, 3)
+    K = K.reshape(V, 3, 3).contiguous()
+    if keep is not None:
+        keep = torch.as_tensor(keep)
+        keep = keep[None] if keep.dim() == 2 else keep
+        if tuple(keep.shape) != (V, H, W):
+            raise ValueError(f"keep must be [{V}, {H}, {W}]")
+    return depth, rgb, K, keep
+
+
+def prepare_frames(depth, rgb, K, num_points: int = 20000, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
+                   flip: bool = False, hash_bits: int = 32, max_groups: int = 0) -> PreparedClouds:
+    """V RGB-D frames of one size -> the network's input (include/gpn.h section FR; the reference's ObjIns.get_pc /
+    get_downsampled_pc, structure/gapartnet.py:541-627).  ``depth`` [V,H,W] f32 / f64 / u16 (divided by ``depth_scale``), ``rgb``
+    [V,H,W,3] u8, ``K`` [V,3,3] or [3,3] (host data), ``keep`` [V,H,W] or None.  Every pixel becomes a row [x y z r g b] (NaN xyz
+    where there is no depth); a frame with more than ``presample * num_points`` valid pixels is cut to that many by the seeded
+    hash rule (``seed``: one uint32 per frame, or an int s for s, s + 1, ...; ``presample`` 0: no cut), then FPS and the ball
+    normalisation of ``prepare_clouds``.  The result's ``source`` is the [V*H*W, 6] rows, its ``sample_rows`` are pixel indices."""
+    depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
+    return _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits, max_groups)
+
+
+def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits=32, max_groups=0):
+    """``prepare_frames`` behind its argument check (``_check_frames``), which the predictor's frame entries run themselves"""
+    V, H, W = (int(v) for v in depth.shape)
+    m, cap = int(num_points), int(presample) * int(num_points)
+    if m < 1 or cap < 0:
+        raise ValueError("num_points must be positive and presample non-negative")
+    seeds = _frame_seeds(seed, V)
+    offsets = [v * H * W for v in range(V + 1)]
+    if depth.is_cuda:
+        from . import backend
+        hip = backend.raw()
+        if hip.name != "hip":
+            raise RuntimeError("prepare_frames on GPU tensors needs the HIP library as the operator backend")
+        got = hip.frame_prepare(depth, rgb, K.to(depth.device, non_blocking=True), m, cap, seeds, keep=keep, depth_scale=depth_scale, flip=flip,
+                                hash_bits=hash_bits, max_groups=max_groups)
+        status = got["status"]
+        counts = torch.where(status == CLOUD_OK, got["counts"], torch.zeros_like(got["counts"]))
+        live = torch.arange(m)[None, :] < counts[:, None]
+        take = torch.nonzero(live.reshape(-1)).squeeze(1).to(depth.device, non_blocking=True)
+        points = got["out"].reshape(V * m, -1).index_select(0, take)
+        sample_rows = got["sample_rows"].reshape(-1).index_select(0, take).long()
+        table = dict(sample_rows=got["sample_rows"], counts=got["counts_dev"], status=got["status_dev"])
+        return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, got["rows"], table)
+    d = depth.numpy()
+    rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), K.numpy(),
+                                     None if keep is None else keep.numpy(), depth_scale, flip)
+    parts = []
+    for v in range(V):
+        frame = rows[offsets[v]:offsets[v + 1]].copy()
+        drop = np.ones(H * W, dtype=bool)
+        drop[select_pixels(np.nonzero(valid[v])[0], seeds[v], cap, hash_bits)] = False
+        frame[drop, :3] = np.nan
+        parts.append(_prepare_cloud_torch(torch.from_numpy(frame), m))
+    return PreparedClouds(torch.cat([p[1] for p in parts]), torch.tensor([p[1].shape[0] for p in parts], dtype=torch.int64),
+                          torch.cat([p[2] for p in parts]), torch.stack([p[3] for p in parts]),
+                          torch.tensor([p[0] for p in parts], dtype=torch.int64), offsets, torch.from_numpy(rows))
+
+
+# the box edges of draw_bbox (structure/utils.py:73-89; include/gpn.h section VS): (corner a, corner b, colour as written, thickness)
+_BOX_DRAWS = [(a, b, (255, 0, 255), 2) for a, b in ((0, 1), (0, 2), (0, 3), (1, 4), (1, 5), (2, 6), (6, 3), (4, 7), (5, 7), (3, 5),
+                                                    (2, 4), (6, 7))] + \
+             [(0, 1, (255, 0, 0), 3), (0, 3, (0, 0, 255), 3), (0, 2, (0, 255, 0), 3)]
+
+
+def _draw_line_numpy(img, a, b, colour, t):
+    """the line rule of include/gpn.h section VS on a host image (what gpn_boxes_draw does on the device)"""
+    H, W = img.shape[:2]
+    pts = np.array([a[0], a[1], b[0], b[1]], dtype=np.float64)
+    if not np.isfinite(pts).all() or not all(-4 * W <= x < 5 * W for x in pts[0::2]) or not all(-4 * H <= y < 5 * H for y in pts[1::2]):
+        return
+    x, y, x1, y1 = (int(p) for p in pts)
+    dx, dy = abs(x1 - x), -abs(y1 - y)
+    sx, sy = (1 if x < x1 else -1), (1 if y < y1 else -1)
+    err = dx + dy
+    while True:
+        tx, ty = x - t // 2, y - t // 2
+        img[max(ty, 0):max(min(ty + t, H), 0), max(tx, 0):max(min(tx + t, W), 0)] = colour
+        if x == x1 and y == y1:
+            return
+        e2 = 2 * err
+        if e2 >= dy:
+            err += dy
+            x += sx
+        if e2 <= dx:
+            err += dx
+            y += sy
+
+
+def project_corners(bbox: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+    """[Q,8,2] f64 (u, v) of box corners [Q,8,3] in the camera frame: rint(x fx / z + cx), rint(y fy / z + cy), half to even
+    (structure/utils.py:70-71; the projection rule of section VS); possibly non-finite"""
+    K = K.to(bbox.device, non_blocking=True)
+    b = bbox.double()
+    u = torch.round(b[..., 0] * K[0, 0] / b[..., 2] + K[0, 2])
+    v = torch.round(b[..., 1] * K[1, 1] / b[..., 2] + K[1, 2])
+    return torch.stack([u, v], -1)
+
+
+def draw_overlays(rgb: torch.Tensor, boxes: Sequence[torch.Tensor], K: torch.Tensor) -> torch.Tensor:
+    """``rgb`` [V,H,W,3] u8 with every frame's boxes (``boxes[v]`` [Q_v,8,3] f64, camera frame) drawn into it by draw_bbox's
+    rule: gpn_boxes_draw with one tile at the origin, edge 0, trans (1, 0, 0, 0) - one launch per distinct K; host loops for CPU"""
+    V, H, W, _ = rgb.shape
+    canvas = rgb.clone().contiguous()
+    if not rgb.is_cuda:
+        img = canvas.numpy()
+        for v in range(V):
+            for corners in project_corners(boxes[v], K[v]).numpy():
+                for a, b, colour, t in _BOX_DRAWS:
+                    _draw_line_numpy(img[v], corners[a], corners[b], colour, t)
+        return canvas
+    from . import backend
+    hip = backend.raw()
+    groups = {}
+    for v in range(V):
+        groups.setdefault(tuple(K[v].reshape(-1).tolist()), []).append(v)
+    for cam, frames in groups.items():
+        # (a group that is not a run of frames draws into a copy of its frames)
+        run = frames == list(range(frames[0], frames[-1] + 1))
+        which = None if run else torch.tensor(frames).to(rgb.device, non_blocking=True)
+        sub = canvas[frames[0]:frames[-1] + 1] if run else canvas.index_select(0, which)
+        bb = torch.cat([boxes[v].double().reshape(-1, 8, 3) for v in frames])
+        scene = torch.cat([torch.full((boxes[v].shape[0],), k, dtype=torch.int32) for k, v in enumerate(frames)]).to(rgb.device, non_blocking=True)
+        trans = torch.tensor([[1.0, 0.0, 0.0, 0.0]] * len(frames), dtype=torch.float64).to(rgb.device, non_blocking=True)
+        if bb.shape[0]:
+            hip.boxes_draw(bb.contiguous(), scene, trans, H, W, cam[0], cam[4], cam[2], cam[5], [(0, 0)], sub, 0)
+        if not run:
+            canvas.index_copy_(0, which, sub)
+    return canvas
+
+
+@dataclass
+class FramePrediction:
+    """one frame of ``PartPredictor.predict_frames`` (``masks``: the per-mask fields of ``predict_frames_with_masks``, else None)"""
+    status: int                     # CLOUD_OK / CLOUD_EMPTY / CLOUD_DEGENERATE
+    scale: torch.Tensor             # [4] f64: (r, cx, cy, cz) of the ball normalisation
+    sem: torch.Tensor               # [H,W] i64: part class of every pixel (0 = no part), -1 where there is no depth
+    instance: torch.Tensor          # [H,W] i64: position (in proposal_scores) of the pixel's part, -1 where none
+    npcs: torch.Tensor              # [H,W,3] f32
+    proposal_scores: torch.Tensor   # [P] f32
+    proposal_classes: torch.Tensor  # [P] i64
+    bbox: torch.Tensor              # [Q,8,3] f64 in the CAMERA frame (un-flipped when the rows were flipped); with masks: one per
+                                    # mask, NaN where the mask has no valid box
+    box_proposal: torch.Tensor      # [Q] i64
+    corners_px: torch.Tensor        # [Q,8,2] f64: the corners' pixels (u, v)
+    overlay: torch.Tensor           # [H,W,3] u8: the frame's RGB with every box drawn (draw_bbox, structure/utils.py:55-90)
+    sample_rows: torch.Tensor       # [m] i64: the sampled pixels (linear indices)
+    masks: Optional["MaskPrediction"] = None
+
+    def to_numpy(self) -> dict:
+        out = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items() if k != "masks"}
+        if self.masks is not None:
+            out.update({"mask_" + f: v for f, v in self.masks.to_numpy().items() if f in MASK_FIELDS})
+        return out
+
+
 # ---------------------------------------------------------------------------------------------------- predictions
 @dataclass
 class PartPrediction:
@@ -292,8 +524,11 @@ class PartPredictor:
 
     @torch.no_grad()
     def predict(self, clouds: Sequence[torch.Tensor], picks: Picks = None) -> List[PartPrediction]:
+        return self._predict_prepared(prepare_clouds(clouds, self.num_points), picks)
+
+    def _predict_prepared(self, prep: PreparedClouds, picks: Picks = None) -> List[PartPrediction]:
+        """everything behind the preparation, shared by ``predict`` (raw clouds) and ``predict_frames`` (RGB-D frames)"""
         model = self.model
-        prep = prepare_clouds(clouds, self.num_points)
         C = prep.source.shape[1]
         if C < model.in_channels:
             raise ValueError(f"the model reads {model.in_channels} columns per point, the clouds have {C}")
@@ -384,8 +619,11 @@ class PartPredictor:
         never a member), ``labels[s]`` [K_s] part classes.  A mask with fewer than ``min_points`` SAMPLED members is dropped (the
         reference's ``sum > 5``, structure/gapartnet.py:635).  Every kept mask is fitted with its OWN NPCS (a point shared by two
         masks carries two predictions); a box needs at least 5 points and a valid fit (the reference's ``<= 4: continue``)."""
+        return self._predict_masks_prepared(prepare_clouds(clouds, self.num_points), masks, labels, picks, min_points)
+
+    def _predict_masks_prepared(self, prep: PreparedClouds, masks, labels, picks: Picks = None, min_points: int = 6) -> List[MaskPrediction]:
+        """everything behind the preparation, shared by ``predict_with_masks`` and ``predict_frames_with_masks``"""
         model = self.model
-        prep = prepare_clouds(clouds, self.num_points)
         C = prep.source.shape[1]
         if C < model.in_channels:
             raise ValueError(f"the model reads {model.in_channels} columns per point, the clouds have {C}")
@@ -482,6 +720,66 @@ class PartPredictor:
                 o.member_npcs = props.npcs_preds[int(cum[g0]):int(cum[g1])]
         return out
 
+    # ------------------------------------------------------------------------------------------------ RGB-D frames
+    def _frame_predictions(self, preds, rgb, K, flip) -> List["FramePrediction"]:
+        V, H, W, _ = rgb.shape
+        unflip = torch.tensor([1.0, -1.0, -1.0] if flip else [1.0, 1.0, 1.0], dtype=torch.float64).to(rgb.device, non_blocking=True)
+        boxes = [p.bbox * unflip for p in preds]
+        overlay = draw_overlays(rgb, boxes, K)
+        return [FramePrediction(status=p.status, scale=p.scale, sem=p.sem.reshape(H, W), instance=p.instance.reshape(H, W),
+                                npcs=p.npcs.reshape(H, W, 3), proposal_scores=p.proposal_scores, proposal_classes=p.proposal_classes,
+                                bbox=boxes[v], box_proposal=p.box_proposal, corners_px=project_corners(boxes[v], K[v]),
+                                overlay=overlay[v], sample_rows=p.sample_rows) for v, p in enumerate(preds)]
+
+    @torch.no_grad()
+    def predict_frames(self, depth, rgb, K, picks: Picks = None, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
+                       flip: bool = False) -> List["FramePrediction"]:
+        """RGB-D frames in (``prepare_frames``), per frame the parts of EVERY pixel as [H,W] maps, one 9-DoF box per part in the
+        camera frame, the boxes' corner pixels and the RGB image with the boxes drawn.  ``flip``: the rows (and so the network's
+        input) have y and z negated, as the reference's ``get_pc`` mode 2; boxes are turned back before they are returned and drawn.
+        Host reads: 6, those of ``predict`` and no more (7 when ``picks`` is a callable) - ONE for the preparation (counts, status,
+        scale), the model's own (voxelisation, proposal stage), post-processing, box selection, ONE for the scenes of the proposals
+        and boxes; ``K`` is host data."""
+        depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
+        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip)
+        return self._frame_predictions(self._predict_prepared(prep, picks), rgb, K, flip)
+
+    @torch.no_grad()
+    def predict_frames_with_masks(self, depth, rgb, K, masks: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], picks: Picks = None,
+                                  min_points: int = 6, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
+                                  flip: bool = False) -> List["FramePrediction"]:
+        """``predict_with_masks`` on frames: ``masks[v]`` [K_v, H, W] bool / u8 pixel masks (SAM's, or given ones;
+        the reference's pixel_mask_to_point_mask), ``labels[v]`` [K_v] part classes.  Flattened, a pixel mask is a mask over the
+        frame's rows.  -> ``FramePrediction`` per frame, its fields PER MASK in the caller's order where ``predict_frames`` has them
+        per part: ``sem`` is the network's own class map; ``masks`` holds the per-mask fields of ``MaskPrediction`` (boxes in the
+        rows' frame); ``bbox`` [K,8,3] / ``corners_px`` [K,8,2] are the masks' boxes in the camera frame, NaN for a mask without a
+        valid box (``masks.valid``); ``overlay`` shows the valid ones (the line rule skips a non-finite corner);
+        ``proposal_scores`` / ``proposal_classes`` are the masks' scores (NaN where dropped) and the caller's labels;
+        ``box_proposal`` = arange(K).  Masks may overlap, so there is no per-pixel part: ``instance`` is -1 and ``npcs`` zero
+        everywhere (the members' NPCS are in ``masks.member_npcs``).  Host reads: 4, those of ``predict_with_masks`` - ONE for the
+        preparation, the model's two (voxelisation, mask stage), ONE for the masks' sizes; nothing behind them has a
+        data-dependent size."""
+        depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
+        V, H, W = (int(v) for v in depth.shape)
+        flat = []
+        for v, mk in enumerate(masks):
+            mk = torch.as_tensor(mk)
+            if mk.dim() != 3 or (mk.shape[0] and tuple(mk.shape[1:]) != (H, W)):
+                raise ValueError(f"frame {v}: masks must be [K, {H}, {W}], got {tuple(mk.shape)}")
+            flat.append(mk.reshape(mk.shape[0], H * W))
+        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip)
+        mp = self._predict_masks_prepared(prep, flat, labels, picks, min_points)
+        dev = rgb.device
+        unflip = torch.tensor([1.0, -1.0, -1.0] if flip else [1.0, 1.0, 1.0], dtype=torch.float64).to(dev, non_blocking=True)
+        boxes = [p.bbox * unflip for p in mp]   # (NaN where not valid: drawn by nobody)
+        overlay = draw_overlays(rgb, boxes, K)
+        return [FramePrediction(status=p.status, scale=p.cloud_scale, sem=p.sem.reshape(H, W),
+                                instance=torch.full((H, W), -1, dtype=torch.int64, device=dev),
+                                npcs=torch.zeros((H, W, 3), dtype=torch.float32, device=dev), proposal_scores=p.score,
+                                proposal_classes=p.label, bbox=boxes[v], box_proposal=torch.arange(boxes[v].shape[0], device=dev),
+                                corners_px=project_corners(boxes[v], K[v]), overlay=overlay[v], sample_rows=p.sample_rows, masks=p)
+                for v, p in enumerate(mp)]
+
 
 # ---------------------------------------------------------------------------------------------------- files and the command line
 def read_obj_points(path: str) -> np.ndarray:
@@ -559,10 +857,97 @@ def _write_panels(preds: Sequence[PartPrediction], names: Sequence[str], out_dir
     return paths
 
 
+def _read_image(path: str) -> np.ndarray:
+    if path.endswith(".npy"):
+        return np.load(path)
+    from PIL import Image
+    return np.asarray(Image.open(path))
+
+
+def _read_depth(path: str) -> np.ndarray:
+    """[H, W] float32 / float64 / uint16 (a 16-bit PNG stays uint16: --depth_scale turns it into metres on the device)"""
+    d = _read_image(path)
+    if d.ndim != 2:
+        raise ValueError(f"{path}: a depth map is [H, W], got {d.shape}")
+    if d.dtype in (np.float32, np.float64, np.uint16):
+        return d
+    if d.dtype.kind in "iu" and d.min() >= 0 and d.max() < 65536:  # (PIL opens 16-bit PNGs as int32 "I")
+        return d.astype(np.uint16)
+    return d.astype(np.float32)
+
+
+def _main_frames(ap, args, model, device) -> int:
+    n = len(args.depth)
+    if args.rgb is None or len(args.rgb) != n or args.intrinsics is None or len(args.intrinsics) not in (1, n):
+        ap.error(f"--depth takes one --rgb per frame ({n}) and --intrinsics once or per frame")
+    if args.keep_mask is not None and len(args.keep_mask) != n:
+        ap.error(f"--keep_mask takes one file per frame ({n}), got {len(args.keep_mask)}")
+    if args.masks is not None and len(args.masks) != n:
+        ap.error(f"--masks takes one file per frame ({n}), got {len(args.masks)}")
+    if args.panels:
+        ap.error("--panels belongs to --input; frames write <name>_overlay.png")
+    depth = [_read_depth(p) for p in args.depth]
+    rgb = [np.ascontiguousarray(_read_image(p)[..., :3]).astype(np.uint8) for p in args.rgb]
+    Ks = [(np.load(p) if p.endswith(".npy") else np.loadtxt(p)).astype(np.float64).reshape(3, 3) for p in args.intrinsics]
+    Ks = Ks * n if len(Ks) == 1 else Ks
+    keep = None if args.keep_mask is None else [(_read_image(p).reshape(d.shape[0], d.shape[1], -1) != 0).any(-1).astype(np.uint8)
+                                                for p, d in zip(args.keep_mask, depth)]
+    given = None
+    if args.masks is not None:
+        given = []
+        for path, d in zip(args.masks, depth):
+            z = np.load(path)
+            m, lab = np.asarray(z["masks"]) != 0, np.asarray(z["labels"]).astype(np.int64).reshape(-1)
+            if m.shape != (lab.shape[0],) + d.shape:
+                ap.error(f"{path}: `masks` must be [K, {d.shape[0]}, {d.shape[1]}] with `labels` [K], got {m.shape} and {lab.shape}")
+            given.append((m, lab))
+    for d, c, p in zip(depth, rgb, args.rgb):
+        if c.shape != d.shape + (3,):
+            ap.error(f"{p}: the image must be [{d.shape[0]}, {d.shape[1]}, 3], got {c.shape}")
+    names = [os.path.splitext(os.path.basename(p))[0] for p in args.depth]
+    os.makedirs(args.out, exist_ok=True)
+    predictor = PartPredictor(model, num_points=args.num_points)
+    preds: List[Optional[FramePrediction]] = [None] * n
+    # (one batch per frame size and depth type)
+    for key in sorted({(d.shape, d.dtype.str) for d in depth}):
+        ids = [i for i, d in enumerate(depth) if (d.shape, d.dtype.str) == key]
+        stack = lambda arrs: torch.from_numpy(np.stack([arrs[i] for i in ids])).to(device)  # noqa: E731
+        kw = dict(presample=args.presample, seed=[(args.seed + i) & 0xffffffff for i in ids], keep=None if keep is None else stack(keep),
+                  depth_scale=args.depth_scale, flip=args.flip)
+        K = torch.from_numpy(np.stack([Ks[i] for i in ids]))
+        if given is None:
+            got = predictor.predict_frames(stack(depth), stack(rgb), K, **kw)
+        else:
+            got = predictor.predict_frames_with_masks(stack(depth), stack(rgb), K, [torch.from_numpy(given[i][0]).to(device) for i in ids],
+                                                      [torch.from_numpy(given[i][1]).to(device) for i in ids], **kw)
+        for i, p in zip(ids, got):
+            preds[i] = p
+    from PIL import Image
+    for name, p in zip(names, preds):
+        arrays = p.to_numpy()
+        np.savez(os.path.join(args.out, name + ".npz"), **arrays)
+        Image.fromarray(arrays["overlay"]).save(os.path.join(args.out, name + "_overlay.png"), compress_level=1)
+        line = f"{name}: {STATUS_NAMES.get(p.status, p.status)}, {p.sem.shape[0]} x {p.sem.shape[1]} pixels"
+        if p.masks is not None:
+            line += f"; {p.masks.kept.shape[0]} masks, {int(p.masks.kept.sum())} kept, {int(p.masks.valid.sum())} boxes"
+        else:
+            line += f", {p.proposal_scores.shape[0]} parts, {p.bbox.shape[0]} boxes"
+        print(line)
+    return 0
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m gapartnet_amd.inference", description=__doc__.split("\n\n")[0])
     ap.add_argument("--ckpt", required=True)
-    ap.add_argument("--input", nargs="+", required=True)
+    ap.add_argument("--input", nargs="+", default=None, help="raw clouds: .npy [N, C >= 3] or .obj")
+    ap.add_argument("--depth", nargs="+", default=None, help="RGB-D frames instead of --input: depth maps, .npy or (16-bit) .png")
+    ap.add_argument("--rgb", nargs="+", default=None, help="one image per depth map")
+    ap.add_argument("--intrinsics", nargs="+", default=None, help="K [3,3] as .txt or .npy: one for all frames or one per frame")
+    ap.add_argument("--depth_scale", type=float, default=1.0, help="depth units per metre (1000 for millimetre PNGs)")
+    ap.add_argument("--keep_mask", nargs="+", default=None, help="one image per frame: non-zero pixels are kept")
+    ap.add_argument("--flip", action="store_true", help="frames: negate y and z of the rows (the reference's get_pc mode 2)")
+    ap.add_argument("--presample", type=int, default=4, help="frames: keep at most presample * num_points pixels before FPS (0: all)")
+    ap.add_argument("--seed", type=int, default=0, help="frames: seed of the presample (frame i of the command line takes seed + i)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--num_points", type=int, default=20000)
     ap.add_argument("--inference_dtype", choices=("fp32", "bf16"), default="fp32")
@@ -575,7 +960,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     device = torch.device(args.device)
     if args.panels and device.type != "cuda":
         ap.error("--panels renders on the GPU (misc/visu.render_panels): it cannot be combined with --device cpu")
+    if (args.input is None) == (args.depth is None):
+        ap.error("give either --input (raw clouds) or --depth / --rgb / --intrinsics (RGB-D frames)")
     model = load_model(args.ckpt, device, args.inference_dtype)
+    if args.depth is not None:
+        return _main_frames(ap, args, model, device)
     clouds = [torch.from_numpy(_read_cloud(p, not args.no_flip)).to(device) for p in args.input]
     given = None
     if args.masks is not None:

@@ -867,6 +867,49 @@ int gpn_cloud_nearest(const float* points, int64_t M, int stride, const int64_t*
                       gpn_stream_t stream);
 
 /* ================================================================================================
+ * FR - RGB-D frames -> the rows and the packed layout of section CP: the front of the reference's deployment path
+ * (structure/gapartnet.py:541-627 ObjIns.get_pc / get_downsampled_pc, structure/utils.py:454-476 get_point_cloud) for a batch of V
+ * frames of one size H x W (V <= 65535).  No host read between the launches; no float atomics; integer atomics only on histograms
+ * and counters, whose results do not depend on their order; every output is bit-reproducible.
+ * gpn_frame_backproject: depth [V,H,W] f32 / f64 / u16 (depth_kind), rgb [V,H,W,3] u8, keep [V,H,W] u8 or NULL (an object mask,
+ *   a depth truncation of the caller's), K [V,3,3] f64 row-major.  z = (double)depth / depth_scale (depth_scale > 0; 1.0 for metres).
+ *   rows [V*H*W, 6] f32, row = pixel in row-major order (u = column, v = line): xyz = the float32 cast of the float64 values
+ *   x = ((u - K02) * z) / K00, y = ((v - K12) * z) / K11, z (structure/utils.py:465-467, the arithmetic and order of section VP);
+ *   flip != 0 negates y and z afterwards (get_pc mode 2, structure/gapartnet.py:576-578); rgb = (float)(u8 / 255.0).
+ *   A pixel is VALID when z is finite and > 0 and keep, if given, is non-zero.  DECISION: the reference keeps depth != 0; a negative
+ *   or non-finite depth has no meaning for a sensor.  DECISION: a valid depth whose x, y or z overflows float32 is invalid as well,
+ *   so that "valid" and "the row's three coordinates are finite" (the rule of section CP) are one set.  The xyz of an invalid pixel
+ *   is NaN (all three) - what gpn_cloud_pack, gpn_cloud_finish and gpn_cloud_nearest treat as "no point"; its rgb is written.
+ *   valid [V,H,W] u8 = 1 / 0 and valid_counts [V] i32 stay on the device.
+ * gpn_frame_select: the seeded presample (the reference's random.sample(range(N), 4 * sampled_num), structure/gapartnet.py:596-601,
+ *   which draws from Python's global generator and cannot be repeated) and the compaction.  DECISION: a counter-based rule, a pure
+ *   function of (seed, pixel).  seeds [V] u32.  With uint32 arithmetic that wraps,
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     h = mix(mix(pixel + seed * 0x9E3779B9) ^ seed),   hq = h >> (32 - hash_bits)   (hash_bits 1 .. 32; callers pass 32)
+ *   a frame with more than cap valid pixels keeps the cap pixels with the smallest 64-bit key (hq << 32) | pixel - the keys are
+ *   unique, so is the set; a frame with at most cap valid pixels keeps all of them; cap == 0 keeps every valid pixel of every frame.
+ *   How: a radix select of the cap-th smallest hq, 8 bits a pass, the digit histograms built in LDS and merged into the frame's
+ *   by integer adds; the threshold t and the number r of pixels with hq == t to admit (lowest pixel first) are resolved on the
+ *   device; then per-chunk counts (a chunk = 1024 pixels, one workgroup), a scan over the chunks, and ballot-ordered stores.
+ *   Outputs in the layout gpn_cloud_pack writes: packed [V, n_bound, 4] f32 = the rows' .xyz and .w = 1e10, n_bound = cap (H*W when
+ *   cap == 0); counts [V] i32 = min(valid, cap); status [V] i32 = GPN_CLOUD_OK or GPN_CLOUD_EMPTY; pix [V, H*W] i32 = the kept
+ *   pixels' linear indices, ascending (the first counts[v] entries are written).  DECISION: pix has the pitch H*W, not n_bound:
+ *   gpn_cloud_finish clamps the row indices it reads to the n_bound it is given, so it takes (pix, n_bound = H*W) while gpn_view_fps
+ *   takes (packed, n_bound = cap); with that, gpn_view_fps, gpn_cloud_finish and gpn_cloud_nearest run unchanged on offsets[v] =
+ *   v * H*W.  cap == 0 equals gpn_cloud_pack on the same rows bit for bit.
+ * ================================================================================================ */
+#define GPN_FRAME_DEPTH_F32 0
+#define GPN_FRAME_DEPTH_F64 1
+#define GPN_FRAME_DEPTH_U16 2
+int gpn_frame_backproject(const void* depth, int depth_kind, double depth_scale, const uint8_t* rgb, const uint8_t* keep,
+                          const double* K, int V, int H, int W, int flip, float* rows, uint8_t* valid, int32_t* valid_counts,
+                          gpn_stream_t stream);
+size_t gpn_frame_select_ws_bytes(int V, int H, int W);
+int gpn_frame_select(const float* rows, const uint8_t* valid, const int32_t* valid_counts, const uint32_t* seeds, int V, int H, int W,
+                     int cap, int hash_bits, int64_t n_bound, float* packed, int32_t* pix, int32_t* counts, int32_t* status, void* ws,
+                     size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * RD - articulated assets -> training views (the reference's dataset/render_tools/render.py without SAPIEN): z-depth, the winning
  * triangle, link labels, the NPCS map and a flat-shaded RGB image for a batch of V views of one size H x W (H, W <= 16384, V <=
  * 65535).  Views may show different assets.  No host read between the launches; no float atomics; every pixel is stored once, so
