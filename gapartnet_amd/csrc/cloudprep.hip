@@ -3,8 +3,8 @@
 //   pack     the rows whose three coordinates are finite, in ascending row order, into the layout gpn_view_fps reads (a scan per
 //            tile, no atomic counter); per-cloud counts and statuses
 //   (fps)    gpn_view_fps as it is (viewprep.hip): counts > m sampled, == m arange, < m flagged = "keep every valid point"
-//   finish   per cloud over its m_s = min(count, m) samples, float64: centre (max + min) / 2, r = sqrt(max((dx^2 + dy^2) + dz^2)),
-//            xyz = float32((p - c) / r) - the formula of vp_finish_kernel; the other columns copied bit for bit
+//   finish   per cloud over its m_s = min(count, m) samples, float64: centre (max + min) / 2, r = sqrt(max((dx^2 + dy^2) + dz^2))
+//            (point_prims.h, ball_of_samples - as gpn_view_finish), xyz = float32((p - c) / r); the other columns copied bit for bit
 //   nearest  for every caller row the nearest sample of its cloud (fp32 (dx^2 + dy^2) + dz^2 without fma, ties to the lowest
 //            sample): a per-cloud uniform grid over the samples' box (histogram, scan, stable scatter), queries walk Chebyshev
 //            rings of cells and stop when no unvisited ring can beat the best distance; exact, with a scan of all samples after
@@ -13,8 +13,11 @@
 #include <cmath>
 
 #include "gpn_common.h"
+#include "point_prims.h"
 
 namespace {
+
+using namespace gpn;
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
@@ -31,13 +34,6 @@ struct CloudGrid {  // per cloud, written by cn_build_kernel
   int n;               // samples (0: the cloud has none - status not OK)
 };
 
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-__device__ __forceinline__ float dist2_nofma(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
 // rows [lo, lo + n) of the caller's array that cloud s owns, clamped so that nothing outside [0, M) or past n_bound is touched
 __device__ __forceinline__ int cloud_rows(const int64_t* offsets, int s, int64_t M, int64_t n_bound, int64_t* lo_out) {
   int64_t lo = offsets[s], hi = offsets[s + 1];
@@ -46,29 +42,6 @@ __device__ __forceinline__ int cloud_rows(const int64_t* offsets, int s, int64_t
   *lo_out = lo;
   const int64_t n = hi - lo;
   return (int)(n < n_bound ? n : n_bound);
-}
-
-// inclusive scan of one int per thread over the workgroup: -> (this thread's inclusive sum, the workgroup's total)
-__device__ __forceinline__ int block_scan(int c, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int s = wsum[w];
-    before += w < wave ? s : 0;
-    tot += s;
-  }
-  __syncthreads();  // wsum is rewritten by the next call
-  *total = tot;
-  return before + incl;
 }
 
 // ---- 1. pack: one workgroup per cloud, tiles of kThreads * kRowsPerThread rows (the compaction of vp_backproject_kernel) ------
@@ -103,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void cp_pack_kernel(const float* __restri
       }
     }
     int total;
-    int pos = base + block_scan(c, wsum, &total) - c;
+    int pos = base + block_scan<kWaves>(c, wsum, &total) - c;
 #pragma unroll
     for (int e = 0; e < kRowsPerThread; ++e) {
       if (vm >> e & 1u) {
@@ -121,17 +94,6 @@ __global__ __launch_bounds__(kThreads) void cp_pack_kernel(const float* __restri
 }
 
 // ---- 2. finish: one workgroup per cloud -----------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_min(double a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) a = fmin(a, __shfl_xor(a, off, 64));
-  return a;
-}
-__device__ __forceinline__ double wave_max(double a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) a = fmax(a, __shfl_xor(a, off, 64));
-  return a;
-}
-
 __global__ __launch_bounds__(kThreads) void cp_finish_kernel(const float* __restrict__ points, int stride, int cols,
                                                              const int64_t* __restrict__ offsets, int64_t M, int64_t n_bound,
                                                              const int32_t* __restrict__ rows, const int32_t* __restrict__ counts,
@@ -139,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void cp_finish_kernel(const float* __rest
                                                              float* __restrict__ out, int32_t* __restrict__ sample_rows,
                                                              double* __restrict__ scale) {
   __shared__ double red[6][kWaves];
-  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x, tid = threadIdx.x;
   const int st = status[s];
   int64_t lo;
   const int n_rows = cloud_rows(offsets, s, M, n_bound, &lo);
@@ -163,37 +125,13 @@ __global__ __launch_bounds__(kThreads) void cp_finish_kernel(const float* __rest
     const int sel = keep_all ? j : min(max(fi[j], 0), n - 1);
     return min(max(rw[sel], 0), n_rows - 1);
   };
-  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int j = tid; j < ms; j += kThreads) {
-    const float* p = src + (int64_t)row_of(j) * stride;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { mn[c] = fmin(mn[c], (double)p[c]); mx[c] = fmax(mx[c], (double)p[c]); }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { mn[c] = wave_min(mn[c]); mx[c] = wave_max(mx[c]); }
-  if (lane == 0)
-    for (int c = 0; c < 3; ++c) { red[c][wave] = mn[c]; red[3 + c][wave] = mx[c]; }
-  __syncthreads();
-  double ctr[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double a = red[c][0], b = red[3 + c][0];
-    for (int q = 1; q < kWaves; ++q) { a = fmin(a, red[c][q]); b = fmax(b, red[3 + c][q]); }
-    ctr[c] = (b + a) / 2.0;  // FindMaxDis: (max + min) / 2
-  }
-  __syncthreads();  // red is reused below
-  double r2 = -INFINITY;
-  for (int j = tid; j < ms; j += kThreads) {
-    const float* p = src + (int64_t)row_of(j) * stride;
-    const double dx = (double)p[0] - ctr[0], dy = (double)p[1] - ctr[1], dz = (double)p[2] - ctr[2];
-    r2 = fmax(r2, (dx * dx + dy * dy) + dz * dz);
-  }
-  r2 = wave_max(r2);
-  if (lane == 0) red[0][wave] = r2;
-  __syncthreads();
-  r2 = red[0][0];
-  for (int q = 1; q < kWaves; ++q) r2 = fmax(r2, red[0][q]);
-  const double r = __dsqrt_rn(r2);  // sqrt is monotonic: sqrt(max) = max(sqrt)
+  double ctr[3], r;
+  ball_of_samples<kWaves>(
+      [&](int j, double* P) {
+        const float* p = src + (int64_t)row_of(j) * stride;
+        P[0] = (double)p[0]; P[1] = (double)p[1]; P[2] = (double)p[2];
+      },
+      ms, red, ctr, &r);
   const bool degenerate = !(r > 0.0);
   for (int j = tid; j < ms; j += kThreads) {
     const int row = row_of(j);
@@ -302,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void cn_build_kernel(const float* __restr
   int sum = 0;
   for (int c = c0; c < c1; ++c) sum += cells[c];
   int total;
-  int run = block_scan(sum, wsum, &total) - sum;
+  int run = block_scan<kWaves>(sum, wsum, &total) - sum;
   for (int c = c0; c < c1; ++c) {
     const int v = cells[c];
     cells[c] = run;

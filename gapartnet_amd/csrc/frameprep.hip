@@ -13,8 +13,11 @@
 #include <cmath>
 
 #include "gpn_common.h"
+#include "point_prims.h"
 
 namespace {
+
+using namespace gpn;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -31,8 +34,6 @@ struct FrameSel {  // per frame, written by fr_count_kernel
   int32_t pad;
 };
 
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 __device__ __forceinline__ uint32_t fr_mix(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352du;
@@ -45,47 +46,6 @@ __device__ __forceinline__ uint32_t fr_mix(uint32_t x) {
 __device__ __forceinline__ uint32_t fr_key(uint32_t seed, uint32_t pixel, int hash_bits) {
   const uint32_t h = fr_mix(fr_mix(pixel + seed * 0x9E3779B9u) ^ seed);
   return hash_bits >= 32 ? h : h >> (32 - hash_bits);
-}
-
-__device__ __forceinline__ int wave_sum(int c) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-  return c;
-}
-
-// sum of one int per thread over the workgroup (every thread gets it)
-__device__ __forceinline__ int block_sum(int c, int* wsum) {
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  int tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) tot += wsum[w];
-  __syncthreads();  // wsum is rewritten by the next call
-  return tot;
-}
-
-// inclusive scan of one int per thread over the workgroup: -> (this thread's inclusive sum, the workgroup's total)
-__device__ __forceinline__ int block_scan(int c, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int s = wsum[w];
-    before += w < wave ? s : 0;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return before + incl;
 }
 
 // ---- 1. back-projection: one workgroup per chunk of a frame ---------------------------------------------------------------------
@@ -126,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void fr_backproject_kernel(const T* __res
     valid[g] = ok ? 1 : 0;
     c += ok ? 1 : 0;
   }
-  const int tot = block_sum(c, wsum);
+  const int tot = block_sum<kWaves>(c, wsum);
   if (tid == 0 && tot > 0) atomicAdd(valid_counts + v, tot);  // (an integer counter: order-free)
 }
 
@@ -141,7 +101,7 @@ __device__ __forceinline__ void fr_resolve(const uint32_t* __restrict__ hist, in
     if (threadIdx.x == 0) { sh[0] = kBins - 1; sh[1] = 1; }  // (never read back unless the histogram is short of k)
     const int h = (int)hist[j * kBins + threadIdx.x];
     int total;
-    const int incl = block_scan(h, wsum, &total);  // (its barriers order the two writes to sh)
+    const int incl = block_scan<kWaves>(h, wsum, &total);  // (its barriers order the two writes to sh)
     if (incl - h < k && k <= incl) { sh[0] = threadIdx.x; sh[1] = k - (incl - h); }
     __syncthreads();
     prefix = (prefix << 8) | (uint32_t)sh[0];
@@ -203,8 +163,8 @@ __global__ __launch_bounds__(kThreads) void fr_count_kernel(const uint8_t* __res
     less += (keep_all || hq < t) ? 1 : 0;
     eq += (!keep_all && hq == t) ? 1 : 0;
   }
-  less = block_sum(less, wsum);
-  eq = block_sum(eq, wsum);
+  less = block_sum<kWaves>(less, wsum);
+  eq = block_sum<kWaves>(eq, wsum);
   if (tid == 0) {
     const int64_t ci = (int64_t)v * gridDim.x + blockIdx.x;
     chunk_less[ci] = less;
@@ -227,9 +187,9 @@ __global__ __launch_bounds__(kThreads) void fr_scan_kernel(const FrameSel* __res
     const int64_t ci = (int64_t)v * nchunk + c;
     const int less = c < nchunk ? chunk_less[ci] : 0, eq = c < nchunk ? chunk_eq[ci] : 0;
     int eq_total, total;
-    const int eq_before = eq_run + block_scan(eq, wsum, &eq_total) - eq;
+    const int eq_before = eq_run + block_scan<kWaves>(eq, wsum, &eq_total) - eq;
     const int kept = less + min(max(r - eq_before, 0), eq);
-    const int before = run + block_scan(kept, wsum, &total) - kept;
+    const int before = run + block_scan<kWaves>(kept, wsum, &total) - kept;
     if (c < nchunk) {
       chunk_eqbase[ci] = eq_before;
       chunk_base[ci] = before;

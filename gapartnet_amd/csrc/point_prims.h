@@ -1,0 +1,228 @@
+// point_prims.h — the building blocks the point front ends share (pointnet2.hip, viewprep.hip, cloudprep.hip, frameprep.hip):
+// the no-fma distance, workgroup integer scan / sum, the furthest-point-sampling candidate with its three reduction steps, and
+// the ball normalisation.  Every one of them is pinned bit for bit by the oracle; this is their only definition.
+#pragma once
+#include "gpn_common.h"
+
+namespace gpn {
+
+// fp32 (dx^2 + dy^2) + dz^2, every operation rounded on its own
+__device__ __forceinline__ float dist2_nofma(float ax, float ay, float az, float bx, float by, float bz) {
+  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
+  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+__device__ __forceinline__ double wave_min(double a) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) a = fmin(a, __shfl_xor(a, off, 64));
+  return a;
+}
+__device__ __forceinline__ double wave_max(double a) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) a = fmax(a, __shfl_xor(a, off, 64));
+  return a;
+}
+
+// ---- one int per thread over a workgroup of kWaves waves; wsum: kWaves ints of LDS, free again when the call returns ----------
+// sum (every thread gets it)
+template <int kWaves>
+__device__ __forceinline__ int block_sum(int c, int* wsum) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  int tot = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) tot += wsum[w];
+  __syncthreads();  // wsum is rewritten by the next call
+  return tot;
+}
+
+// inclusive scan: -> (this thread's inclusive sum, the workgroup's total)
+template <int kWaves>
+__device__ __forceinline__ int block_scan(int c, int* wsum, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int before = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const int s = wsum[w];
+    before += w < wave ? s : 0;
+    tot += s;
+  }
+  __syncthreads();  // wsum is rewritten by the next call
+  *total = tot;
+  return before + incl;
+}
+
+// ---- furthest point sampling: the candidate (running distance, point index) and its reduction ---------------------------------
+// The arg-max reproduces the reference's result (sampling_gpu.cu:93-209) for ITS block size Bref = opt_n_threads(n): highest
+// distance, ties to the lowest reference thread id (k mod Bref) in the order of its tree, then to the lowest k.  A total order: any
+// split of a cloud's points over threads, waves and workgroups gives the same winner.
+struct FpsCand {
+  float v;
+  int k;
+};
+
+// opt_n_threads(n) - 1 (cuda_utils.h:10-14): the largest power of two <= n, at most 1024, less one.  The reference's
+// (int)(log(n) / log(2)) equals floor(log2(n)) for every n in [1, 2^21] (tests/test_convert_cpu.py), and n >= 1024 gives 1024.
+__host__ __device__ __forceinline__ int fps_bmask(int n) {
+  const int v = n >= 1024 ? 1024 : (1 << (31 - __builtin_clz((unsigned)n)));
+  return v - 1;
+}
+
+__device__ __forceinline__ bool fps_better(float av, int ak, float bv, int bk, int bmask) {
+  if (av != bv) return av > bv;
+  // the reference's tree (sampling_gpu.cu:143-200) merges slot j with j+s for s = B/2 ... 1 and keeps slot j on
+  // ties, so two tied candidates are decided at the lowest bit where their thread ids differ, the 0-bit winning:
+  // ascending order of the bit-reversed thread id
+  const unsigned ta = __brev((unsigned)(ak & bmask)), tb = __brev((unsigned)(bk & bmask));
+  if (ta != tb) return ta < tb;
+  return ak < bk;
+}
+
+// the wave's best candidate, in lane 0
+__device__ __forceinline__ FpsCand fps_wave_best(FpsCand c, int bmask) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ov = __shfl_down(c.v, off, 64);
+    const int ok = __shfl_down(c.k, off, 64);
+    if (lane + off < 64 && fps_better(ov, ok, c.v, c.k, bmask)) { c.v = ov; c.k = ok; }
+  }
+  return c;
+}
+
+// the workgroup's best candidate, in lane 0 of wave 0 (other threads: unspecified); wv / wk: kWaves words of LDS each.  A barrier
+// must separate the caller's reads of the result from the next call.
+template <int kWaves>
+__device__ __forceinline__ FpsCand fps_block_best(FpsCand c, int bmask, float* wv, int* wk) {
+  static_assert(kWaves == 16, "the tree below folds 16 wave candidates");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  c = fps_wave_best(c, bmask);
+  if (lane == 0) { wv[wave] = c.v; wk[wave] = c.k; }
+  __syncthreads();
+  if (wave == 0) {
+    c.v = lane < kWaves ? wv[lane] : -2.f;
+    c.k = lane < kWaves ? wk[lane] : 0x7fffffff;
+#pragma unroll
+    for (int off = kWaves / 2; off >= 1; off >>= 1) {
+      const float ov = __shfl_down(c.v, off, 64);
+      const int ok = __shfl_down(c.k, off, 64);
+      if (fps_better(ov, ok, c.v, c.k, bmask)) { c.v = ov; c.k = ok; }
+    }
+  }
+  return c;
+}
+
+// The j-th meeting (j = 1, 2, ...) of the G <= 64 workgroups that share a cloud, called by ONE whole wave of each: member w
+// publishes its candidate (lane 0's `c`) in the double-buffered slot (j & 1) * G + w of cv / ck [2][G], all G meet at `counter`
+// (zeroed by the host before the launch), and every member reduces the G candidates itself, so the winner (in lane 0) never has
+// to be broadcast.  The counter is never reset: the j-th meeting waits for G * j (fps_meetings_fit bounds it).  Every workgroup
+// of the launch must be resident: cooperative launches only (fps_launch).
+__device__ __forceinline__ FpsCand fps_meet(FpsCand c, int j, int G, int w, int bmask, float* cv, int* ck, unsigned* counter) {
+  const int lane = threadIdx.x & 63;
+  const int slot = (j & 1) * G;
+  if (lane == 0) {
+    __hip_atomic_store(cv + slot + w, c.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ck + slot + w, c.k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned want = (unsigned)G * (unsigned)j;
+    while (__hip_atomic_load(counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) __builtin_amdgcn_s_sleep(1);
+    __threadfence();
+  }
+  // lane 0 has passed the barrier; the wave re-converges here and reads every workgroup's candidate
+  __threadfence();  // every lane: the candidate reads below stay behind lane 0's acquire
+  c.v = -2.f;
+  c.k = 0x7fffffff;
+  if (lane < G) {
+    c.v = __hip_atomic_load(cv + slot + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c.k = __hip_atomic_load(ck + slot + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return fps_wave_best(c, bmask);
+}
+
+// ---- host side of fps_meet ------------------------------------------------------------------------------------------------------
+// The bound on a launch's meetings: the 32-bit counter of fps_meet reaches (m - 1) * G; the host keeps m * G below 2^31.
+inline bool fps_meetings_fit(int m, int G) { return (int64_t)m * G < (int64_t)0x7fffffff; }
+
+// Launch an FPS kernel of 1024-thread workgroups for entry point `who`; `args` hold the kernels' (common) arguments, *G among them:
+// the workgroups per cloud, grid = wgs_per_group * G.  *G > 1: zero the `counters` arrival counters and launch `shared`
+// cooperatively - the runtime starts the grid only when ALL its workgroups can be resident at once (and refuses a grid that
+// cannot be), which is what the in-kernel counter meeting needs: a plain launch next to other streams' kernels, other ranks
+// sharing the device or a CU mask could leave some workgroups unscheduled while the resident ones spin.  Refused (not
+// co-schedulable here: too large for this device / partition): the error is cleared and `single` runs with *G = 1, the form
+// without any inter-workgroup wait.
+inline int fps_launch(const char* who, const void* shared, const void* single, unsigned wgs_per_group, int* G, void** args,
+                      unsigned* arrived, size_t counters, hipStream_t stream) {
+  if (*G > 1) {
+    hipError_t e = hipMemsetAsync(arrived, 0, counters * sizeof(unsigned), stream);
+    if (e != hipSuccess) {
+      gpn::set_error("%s: hipMemsetAsync of the arrival counters failed: %s", who, hipGetErrorString(e));
+      return GPN_ERR_HIP;
+    }
+    if (hipLaunchCooperativeKernel(shared, dim3(wgs_per_group * (unsigned)*G), dim3(1024), args, 0, stream) == hipSuccess) return GPN_OK;
+    (void)hipGetLastError();
+    *G = 1;
+  }
+  hipError_t e = hipLaunchKernel(single, dim3(wgs_per_group), dim3(1024), args, 0, stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) {
+    gpn::set_error("%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    return GPN_ERR_HIP;
+  }
+  return GPN_OK;
+}
+
+// ---- ball normalisation (convert_rendered_into_input.py:71-87, FindMaxDis) -------------------------------------------------------
+// Over the m >= 1 samples a workgroup of kWaves waves owns, float64: centre (max + min) / 2 per axis, r = sqrt(max((dx^2 + dy^2) +
+// dz^2)) - to every thread.  sample(j, P) writes sample j's coordinates to double P[3]; it is called twice per sample.  Minima and
+// maxima are exact in any order, and the square root is monotonic, so sqrt(max) = max(sqrt).  red: LDS, read until the return.
+template <int kWaves, typename Sample>
+__device__ __forceinline__ void ball_of_samples(Sample sample, int m, double (*red)[kWaves] /* [6] */, double ctr[3], double* r) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, threads = kWaves * 64;
+  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int j = tid; j < m; j += threads) {
+    double P[3];
+    sample(j, P);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { mn[c] = fmin(mn[c], P[c]); mx[c] = fmax(mx[c], P[c]); }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { mn[c] = wave_min(mn[c]); mx[c] = wave_max(mx[c]); }
+  if (lane == 0)
+    for (int c = 0; c < 3; ++c) { red[c][wave] = mn[c]; red[3 + c][wave] = mx[c]; }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double a = red[c][0], b = red[3 + c][0];
+    for (int q = 1; q < kWaves; ++q) { a = fmin(a, red[c][q]); b = fmax(b, red[3 + c][q]); }
+    ctr[c] = (b + a) / 2.0;
+  }
+  __syncthreads();  // red is reused below
+  double r2 = -INFINITY;
+  for (int j = tid; j < m; j += threads) {
+    double P[3];
+    sample(j, P);
+    const double dx = P[0] - ctr[0], dy = P[1] - ctr[1], dz = P[2] - ctr[2];
+    r2 = fmax(r2, (dx * dx + dy * dy) + dz * dz);
+  }
+  r2 = wave_max(r2);
+  if (lane == 0) red[0][wave] = r2;
+  __syncthreads();
+  r2 = red[0][0];
+  for (int q = 1; q < kWaves; ++q) r2 = fmax(r2, red[0][q]);
+  *r = __dsqrt_rn(r2);
+}
+
+}  // namespace gpn

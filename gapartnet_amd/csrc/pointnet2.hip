@@ -4,15 +4,13 @@
 #include <cmath>
 
 #include "gpn_common.h"
+#include "point_prims.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace gpn;
 
-__device__ __forceinline__ float dist2_nofma(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
+constexpr int kThreads = 256;
 
 // ---- ball_query_gpu.cu:9-45 : thread per query, candidates broadcast from LDS tiles ----------------
 __global__ __launch_bounds__(kThreads) void pn2_ball_query_kernel(int n, int m, float radius2, int nsample,
@@ -90,66 +88,50 @@ __global__ void pn2_gather_points_grad_kernel(int c, int n, int m, const float* 
 }
 
 // ---- sampling_gpu.cu:93-209 : furthest point sampling ----------------------------------------------
-// One 1024-thread workgroup per cloud.  The arg-max reproduces the reference's result for ITS block size
-// Bref = opt_n_threads(n): highest distance, ties to the lowest reference thread id (k mod Bref), then
-// to the lowest k.  Wave-level reduction by shuffles, cross-wave through LDS.
-struct FpsCand {
-  float v;
-  int k;
-};
-__device__ __forceinline__ bool fps_better(float av, int ak, float bv, int bk, int bmask) {
-  if (av != bv) return av > bv;
-  // the reference's tree (sampling_gpu.cu:143-200) merges slot j with j+s for s = B/2 ... 1 and keeps slot j on
-  // ties, so two tied candidates are decided at the lowest bit where their thread ids differ, the 0-bit winning:
-  // ascending order of the bit-reversed thread id
-  const unsigned ta = __brev((unsigned)(ak & bmask)), tb = __brev((unsigned)(bk & bmask));
-  if (ta != tb) return ta < tb;
-  return ak < bk;
-}
-
-__global__ __launch_bounds__(1024) void pn2_fps_kernel(int n, int m, int bmask, const float* __restrict__ dataset,
-                                                       float* __restrict__ temp, int32_t* __restrict__ idxs) {
+// 1024-thread workgroups; the candidate order and its reduction steps are point_prims.h's, so the samples are the reference's for
+// ITS block size in either form.  One body, two instantiations with one argument list:
+//   kShared = false  one workgroup per cloud (G, cand_v, cand_k, arrived unused): it streams the cloud's n points every iteration
+//                    and waits for nobody - every cloud below 65536 points, the training sampler among them
+//   kShared = true   big clouds (pre-processing: N ~ 1e5..1e6 -> 20 000 samples; one workgroup moves 16 MB per iteration at N =
+//                    1e6: ~200 us, x 20 000) are shared by G > 1 workgroups: member w owns a contiguous chunk of the points (and
+//                    of `temp`), reduces it to one candidate, and meets the others at the cloud's counter (fps_meet).  All b * G
+//                    workgroups must be resident at once (b * G <= number of CUs; the host picks G accordingly).
+template <bool kShared>
+__global__ __launch_bounds__(1024) void pn2_fps_kernel(int n, int m, int bmask, int G, const float* __restrict__ dataset,
+                                                       float* __restrict__ temp, int32_t* __restrict__ idxs,
+                                                       float* cand_v /* [b][2][G] */, int* cand_k /* [b][2][G] */,
+                                                       unsigned* arrived /* [b] */) {
   __shared__ float wv[16];
   __shared__ int wk[16];
   __shared__ int s_old;
-  const int bs = blockIdx.x;
+  const int bs = kShared ? blockIdx.x / G : blockIdx.x, w = kShared ? blockIdx.x - bs * G : 0;
   const float* d = dataset + (int64_t)bs * n * 3;
   float* t = temp + (int64_t)bs * n;
   int32_t* out = idxs + (int64_t)bs * m;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int chunk = kShared ? (n + G - 1) / G : n;
+  const int lo = w * chunk, hi = lo + chunk < n ? lo + chunk : n;
   int old = 0;
-  if (tid == 0) out[0] = 0;
+  if (w == 0 && tid == 0) out[0] = 0;
   for (int j = 1; j < m; ++j) {
     const float x1 = d[old * 3], y1 = d[old * 3 + 1], z1 = d[old * 3 + 2];
-    float best = -1.f;
-    int besti = 0;
-    for (int k = tid; k < n; k += 1024) {
+    // a thread's points share k & bmask (k steps by 1024): within the thread, the larger distance then the lower k wins.  A
+    // thread with no point carries (-1, INT_MAX): never better than a real candidate (distances are >= 0)
+    FpsCand c = {-1.f, 0x7fffffff};
+    for (int k = lo + tid; k < hi; k += 1024) {
       const float dd = dist2_nofma(d[k * 3], d[k * 3 + 1], d[k * 3 + 2], x1, y1, z1);
       const float tk = t[k];
       const float d2 = dd < tk ? dd : tk;
       t[k] = d2;
-      if (d2 > best) { best = d2; besti = k; }
+      if (d2 > c.v) { c.v = d2; c.k = k; }
     }
-    // threads with no point (tid >= n) carry (-1, tid): never better than a real candidate
-    if (tid >= n) besti = tid;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float ov = __shfl_down(best, off, 64);
-      const int ok = __shfl_down(besti, off, 64);
-      if (lane + off < 64 && fps_better(ov, ok, best, besti, bmask)) { best = ov; besti = ok; }
-    }
-    if (lane == 0) { wv[wave] = best; wk[wave] = besti; }
-    __syncthreads();
+    c = fps_block_best<16>(c, bmask, wv, wk);
     if (wave == 0) {
-      float v = lane < 16 ? wv[lane] : -2.f;
-      int k = lane < 16 ? wk[lane] : 0x7fffffff;
-#pragma unroll
-      for (int off = 8; off >= 1; off >>= 1) {
-        const float ov = __shfl_down(v, off, 64);
-        const int ok = __shfl_down(k, off, 64);
-        if (fps_better(ov, ok, v, k, bmask)) { v = ov; k = ok; }
+      if (kShared) c = fps_meet(c, j, G, w, bmask, cand_v + (int64_t)bs * 2 * G, cand_k + (int64_t)bs * 2 * G, arrived + bs);
+      if (lane == 0) {
+        s_old = c.k;
+        if (w == 0) out[j] = c.k;
       }
-      if (lane == 0) { s_old = k; out[j] = k; }
     }
     __syncthreads();
     old = s_old;
@@ -254,14 +236,6 @@ __global__ void pn2_three_interpolate_grad_kernel(int c, int n, int m, const flo
   atomicAdd(gp + id[2], __fmul_rn(g, w[2]));
 }
 
-int opt_n_threads(int work_size) {  // cuda_utils.h:10-14
-  const int pow_2 = (int)(std::log((double)work_size) / std::log(2.0));
-  int v = 1 << pow_2;
-  if (v > 1024) v = 1024;
-  if (v < 1) v = 1;
-  return v;
-}
-
 }  // namespace
 
 extern "C" int gpn_pn2_ball_query(int b, int n, int m, float radius, int nsample, const float* new_xyz,
@@ -323,115 +297,32 @@ extern "C" int gpn_pn2_gather_points_grad(int b, int c, int n, int npoints, cons
   return GPN_OK;
 }
 
-// ---- the same sampling for big clouds (pre-processing: N ~ 1e5..1e6 -> 20 000 samples) -------------------------------
-// One workgroup streams all N points through one CU every iteration (16 MB per iteration at N = 1e6: ~200 us, x 20 000).
-// Here G workgroups share a cloud: each owns a contiguous chunk of the points (and of `temp`), reduces its chunk to one
-// candidate, publishes it, and all G meet at a counter barrier; every workgroup then reduces the G candidates itself, so
-// the winner never has to be broadcast.  The candidate order is the single-workgroup kernel's (fps_better: distance, then
-// the reference's thread-id tie-break, then index), so the samples are identical.  All b * G workgroups must be resident
-// at once (b * G <= number of CUs; the host picks G accordingly).
-__global__ __launch_bounds__(1024) void pn2_fps_multi_kernel(int n, int m, int bmask, int G,
-                                                             const float* __restrict__ dataset, float* __restrict__ temp,
-                                                             int32_t* __restrict__ idxs, float* cand_v /* [b][2][G] */,
-                                                             int* cand_k /* [b][2][G] */, unsigned* arrived /* [b] */) {
-  __shared__ float wv[16];
-  __shared__ int wk[16];
-  __shared__ int s_old;
-  const int bs = blockIdx.x / G, w = blockIdx.x - bs * G;
-  const float* d = dataset + (int64_t)bs * n * 3;
-  float* t = temp + (int64_t)bs * n;
-  int32_t* out = idxs + (int64_t)bs * m;
-  float* cv = cand_v + (int64_t)bs * 2 * G;
-  int* ck = cand_k + (int64_t)bs * 2 * G;
-  unsigned* counter = arrived + bs;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int chunk = (n + G - 1) / G;
-  const int lo = w * chunk, hi = lo + chunk < n ? lo + chunk : n;
-  int old = 0;
-  if (w == 0 && tid == 0) out[0] = 0;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = d[old * 3], y1 = d[old * 3 + 1], z1 = d[old * 3 + 2];
-    float best = -1.f;
-    int besti = 0x7fffffff;
-    for (int k = lo + tid; k < hi; k += 1024) {
-      const float dd = dist2_nofma(d[k * 3], d[k * 3 + 1], d[k * 3 + 2], x1, y1, z1);
-      const float tk = t[k];
-      const float d2 = dd < tk ? dd : tk;
-      t[k] = d2;
-      if (fps_better(d2, k, best, besti, bmask)) { best = d2; besti = k; }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float ov = __shfl_down(best, off, 64);
-      const int ok = __shfl_down(besti, off, 64);
-      if (lane + off < 64 && fps_better(ov, ok, best, besti, bmask)) { best = ov; besti = ok; }
-    }
-    if (lane == 0) { wv[wave] = best; wk[wave] = besti; }
-    __syncthreads();
-    const int slot = (j & 1) * G;
-    if (wave == 0) {
-      float v = lane < 16 ? wv[lane] : -2.f;
-      int k = lane < 16 ? wk[lane] : 0x7fffffff;
-#pragma unroll
-      for (int off = 8; off >= 1; off >>= 1) {
-        const float ov = __shfl_down(v, off, 64);
-        const int ok = __shfl_down(k, off, 64);
-        if (fps_better(ov, ok, v, k, bmask)) { v = ov; k = ok; }
-      }
-      if (lane == 0) {
-        __hip_atomic_store(cv + slot + w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(ck + slot + w, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned want = (unsigned)G * (unsigned)j;  // j-th meeting of G workgroups (m * G < 2^32: host-checked)
-        while (__hip_atomic_load(counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) __builtin_amdgcn_s_sleep(1);
-        __threadfence();
-      }
-      // lane 0 has passed the barrier; the wave re-converges here and reads every workgroup's candidate (G <= 64)
-      __threadfence();  // every lane: the candidate reads below stay behind lane 0's acquire
-      float gv = -2.f;
-      int gk = 0x7fffffff;
-      if (lane < G) {
-        gv = __hip_atomic_load(cv + slot + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        gk = __hip_atomic_load(ck + slot + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_down(gv, off, 64);
-        const int ok = __shfl_down(gk, off, 64);
-        if (lane + off < 64 && fps_better(ov, ok, gv, gk, bmask)) { gv = ov; gk = ok; }
-      }
-      if (lane == 0) {
-        s_old = gk;
-        if (w == 0) out[j] = gk;
-      }
-    }
-    __syncthreads();
-    old = s_old;
-  }
+// the sampling kernel with G workgroups per cloud for entry point `who` (fps_launch: G > 1 cooperatively, or else one per cloud)
+static int fps_run(const char* who, int b, int n, int m, int G, const float* dataset, float* temp, int32_t* idxs, float* cand_v,
+                   int* cand_k, unsigned* arrived, hipStream_t stream) {
+  int bmask = fps_bmask(n);
+  void* args[] = {&n, &m, &bmask, &G, &dataset, &temp, &idxs, &cand_v, &cand_k, &arrived};
+  return fps_launch(who, (const void*)pn2_fps_kernel<true>, (const void*)pn2_fps_kernel<false>, (unsigned)b, &G, args, arrived,
+                    (size_t)b, stream);
 }
 
 extern "C" int gpn_pn2_furthest_point_sampling(int b, int n, int m, const float* dataset, float* temp,
                                                int32_t* idxs, gpn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   GPN_CHECK_ARG(b >= 0 && n >= 1 && m >= 0);
   if (b == 0 || m == 0) return GPN_OK;
   GPN_CHECK_ARG(dataset && temp && idxs);
-  const int bref = opt_n_threads(n);
-  hipLaunchKernelGGL(pn2_fps_kernel, dim3(b), dim3(1024), 0, stream, n, m, bref - 1, dataset, temp, idxs);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  return fps_run(__func__, b, n, m, 1, dataset, temp, idxs, nullptr, nullptr, nullptr, (hipStream_t)stream_);
 }
 
-// workgroups per cloud of the multi-workgroup form: as many as are guaranteed to be resident together (occupancy query x
-// CU count; the kernel meets at a counter barrier, so every workgroup of a cloud must be running), at most 64 (one wave
-// reduces the candidates), none for clouds a single workgroup handles faster than a chip-wide barrier per sample costs
+// workgroups per cloud: as many as are guaranteed to be resident together (occupancy query x CU count; the kernel meets at a
+// counter, so every workgroup of a cloud must be running), at most 64 (one wave reduces the candidates), one for clouds a single
+// workgroup handles faster than a chip-wide meeting per sample costs
 static int fps_groups(int b, int n) {
   if (n < 65536 || b < 1) return 1;
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pn2_fps_multi_kernel, 1024, 0) != hipSuccess || per_cu < 1) {
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pn2_fps_kernel<true>, 1024, 0) != hipSuccess || per_cu < 1) {
     (void)hipGetLastError();
     return 1;
   }
@@ -449,31 +340,18 @@ extern "C" size_t gpn_pn2_furthest_point_sampling_ws_bytes(int b, int n) {
 
 extern "C" int gpn_pn2_furthest_point_sampling_ws(int b, int n, int m, const float* dataset, float* temp, int32_t* idxs,
                                                   void* ws, size_t ws_bytes, gpn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   GPN_CHECK_ARG(b >= 0 && n >= 1 && m >= 0);
   if (b == 0 || m == 0) return GPN_OK;
   const int G = fps_groups(b, n);
   if (G == 1) return gpn_pn2_furthest_point_sampling(b, n, m, dataset, temp, idxs, stream_);
   GPN_CHECK_ARG(dataset && temp && idxs);
-  GPN_CHECK_ARG((int64_t)m * G < (int64_t)0x7fffffff);
+  GPN_CHECK_ARG(fps_meetings_fit(m, G));
   gpn::WsCarver carve(ws, ws_bytes);
   float* cand_v = carve.take<float>((size_t)b * 2 * G);
   int* cand_k = carve.take<int>((size_t)b * 2 * G);
   unsigned* arrived = carve.take<unsigned>((size_t)b);
   GPN_CHECK_WS(carve);
-  GPN_CHECK_HIP(hipMemsetAsync(arrived, 0, (size_t)b * sizeof(unsigned), stream));
-  const int bref = opt_n_threads(n);
-  // cooperative launch: the runtime starts the grid only when ALL its workgroups can be resident at once (and refuses a
-  // grid that cannot be), which is what the in-kernel counter barrier needs - a plain launch next to other streams' kernels,
-  // other ranks sharing the device or a CU mask could leave some workgroups unscheduled while the resident ones spin.
-  int bmask = bref - 1, groups = G;
-  void* args[] = {&n, &m, &bmask, &groups, &dataset, &temp, &idxs, &cand_v, &cand_k, &arrived};
-  const hipError_t err = hipLaunchCooperativeKernel((const void*)pn2_fps_multi_kernel, dim3(b * G), dim3(1024), args, 0, stream);
-  if (err != hipSuccess) {  // not co-schedulable here (too large for this device / partition): single-workgroup form
-    (void)hipGetLastError();
-    return gpn_pn2_furthest_point_sampling(b, n, m, dataset, temp, idxs, stream_);
-  }
-  return GPN_OK;
+  return fps_run(__func__, b, n, m, G, dataset, temp, idxs, cand_v, cand_k, arrived, (hipStream_t)stream_);
 }
 
 extern "C" int gpn_pn2_three_nn(int b, int n, int m, const float* unknown, const float* known, float* dist2,

@@ -9,8 +9,11 @@
 #include <cmath>
 
 #include "gpn_common.h"
+#include "point_prims.h"
 
 namespace {
+
+using namespace gpn;
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
@@ -26,31 +29,9 @@ __device__ __forceinline__ double depth_at(const void* depth, int depth_f64, int
 // reference :58-59, float64, left to right: ((pix - c) * z) / f  (-ffp-contract=off: no fused multiply-add)
 __device__ __forceinline__ double unproject(int pix, double c, double z, double f) { return (((double)pix - c) * z) / f; }
 
-__device__ __forceinline__ float dist2_nofma(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// the candidate order of pointnet2.hip (fps_better): distance, then the reference's block-reduction tie-break for its block
-// size opt_n_threads(n) (bit-reversed thread id k & bmask), then index.  A total order: any split of a view's points over
-// workgroups gives the same winner.
-__device__ __forceinline__ bool fps_better(float av, int ak, float bv, int bk, int bmask) {
-  if (av != bv) return av > bv;
-  const unsigned ta = __brev((unsigned)(ak & bmask)), tb = __brev((unsigned)(bk & bmask));
-  if (ta != tb) return ta < tb;
-  return ak < bk;
-}
-
-// opt_n_threads(n) - 1 (cuda_utils.h:10-14): the largest power of two <= n, at most 1024.  The host form
-// (int)(log(n) / log(2)) equals floor(log2(n)) for every n in [1, 2^21] (tests/test_convert_cpu.py), and n >= 1024 gives 1024.
-__device__ __forceinline__ int fps_bmask(int n) {
-  const int v = n >= 1024 ? 1024 : (1 << (31 - __clz(n)));
-  return v - 1;
-}
-
 // ---- 1. back-projection + stable compaction: one workgroup per view, tiles of kThreads * kPixPerThread pixels ----------------
-// A thread takes kPixPerThread consecutive pixels; an inclusive shuffle scan of the per-thread counts inside each wave and a scan
-// of the 16 wave totals give every valid pixel its row-major rank; the running tile base is the cross-tile scan.
+// A thread takes kPixPerThread consecutive pixels; an inclusive scan of the per-thread counts over the workgroup (block_scan)
+// gives every valid pixel its row-major rank; the running tile base is the cross-tile scan.
 __global__ __launch_bounds__(kThreads) void vp_backproject_kernel(const void* __restrict__ depth, int depth_f64,
                                                                   const int32_t* __restrict__ sem,
                                                                   const int32_t* __restrict__ ins,
@@ -62,7 +43,7 @@ __global__ __launch_bounds__(kThreads) void vp_backproject_kernel(const void* __
   const int64_t HW = (int64_t)H * W, off = (int64_t)v * HW;
   const double* K = Ks + (int64_t)v * 9;
   const double fx = K[0], cx = K[2], fy = K[4], cy = K[5];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int base = 0, bad = 0;
   for (int64_t p0 = 0; p0 < HW; p0 += kThreads * kPixPerThread) {
     const int64_t q0 = p0 + (int64_t)tid * kPixPerThread;
@@ -80,22 +61,8 @@ __global__ __launch_bounds__(kThreads) void vp_backproject_kernel(const void* __
         }
       }
     }
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int s = wsum[w];
-      before += w < wave ? s : 0;
-      total += s;
-    }
-    int pos = base + before + incl - c;
+    int total;
+    int pos = base + block_scan<kWaves>(c, wsum, &total) - c;
 #pragma unroll
     for (int e = 0; e < kPixPerThread; ++e) {
       if (vm >> e & 1u) {
@@ -109,7 +76,6 @@ __global__ __launch_bounds__(kThreads) void vp_backproject_kernel(const void* __
       }
     }
     base += total;
-    __syncthreads();  // wsum is rewritten by the next tile
   }
   bad = __syncthreads_or(bad);
   if (tid == 0) {
@@ -121,10 +87,10 @@ __global__ __launch_bounds__(kThreads) void vp_backproject_kernel(const void* __
 // ---- 2. ragged multi-view FPS ------------------------------------------------------------------------------------------------
 // G workgroups per view; member w owns the contiguous chunk [lo, hi) of the view's n points.  The first kPpt * kThreads points of
 // the chunk and their running distances live in VGPRs for all m iterations; the rest (views larger than G * kPpt * kThreads
-// points) stream through memory with the running distance in .w.  Per sample: the chunk's candidate by wave shuffles and LDS,
-// then (G > 1) one exchange of the G (value, index) candidates at a per-view counter, as pn2_fps_multi_kernel does.  G == 1: no
-// inter-workgroup wait at all.  Workgroup i serves view (i / 8 / G) * 8 + i % 8: the G members of a view share i % 8, the XCD of
-// round-robin dispatch (speed only).
+// points) stream through memory with the running distance in .w.  Per sample: the chunk's candidate (point_prims.h: the candidate
+// order of gpn_pn2_furthest_point_sampling for the view's own n, fps_block_best), then (G > 1) one exchange of the G candidates at
+// a per-view counter (fps_meet).  G == 1: no inter-workgroup wait at all.  Workgroup i serves view (i / 8 / G) * 8 + i % 8: the G
+// members of a view share i % 8, the XCD of round-robin dispatch (speed only).
 __global__ __launch_bounds__(kThreads) void vp_fps_kernel(float4* __restrict__ points, int64_t n_bound,
                                                           const int32_t* __restrict__ counts, int32_t* __restrict__ status,
                                                           int V, int m, int G, int32_t* __restrict__ idxs, float* cand_v,
@@ -174,67 +140,27 @@ __global__ __launch_bounds__(kThreads) void vp_fps_kernel(float4* __restrict__ p
     const float* o = reinterpret_cast<const float*>(d + old);
     const float x1 = o[0], y1 = o[1], z1 = o[2];
     // a thread's points share k & bmask (k steps by 1024): within the thread, the larger distance then the lower k wins
-    float best = -1.f;
-    int besti = 0x7fffffff;
+    FpsCand c = {-1.f, 0x7fffffff};
 #pragma unroll
     for (int e = 0; e < kPpt; ++e) {
       const float dd = dist2_nofma(px[e], py[e], pz[e], x1, y1, z1);
       const float d2 = dd < pd[e] ? dd : pd[e];
       pd[e] = d2;
-      if (d2 > best) { best = d2; besti = lo + tid + e * kThreads; }
+      if (d2 > c.v) { c.v = d2; c.k = lo + tid + e * kThreads; }
     }
     for (int k = rlo + tid; k < hi; k += kThreads) {
       const float4 q = d[k];
       const float dd = dist2_nofma(q.x, q.y, q.z, x1, y1, z1);
       const float d2 = dd < q.w ? dd : q.w;
       reinterpret_cast<float*>(d + k)[3] = d2;
-      if (d2 > best) { best = d2; besti = k; }
+      if (d2 > c.v) { c.v = d2; c.k = k; }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float ov = __shfl_down(best, off, 64);
-      const int ok = __shfl_down(besti, off, 64);
-      if (lane + off < 64 && fps_better(ov, ok, best, besti, bmask)) { best = ov; besti = ok; }
-    }
-    if (lane == 0) { wv[wave] = best; wk[wave] = besti; }
-    __syncthreads();
+    c = fps_block_best<kWaves>(c, bmask, wv, wk);
     if (wave == 0) {
-      float bv = lane < kWaves ? wv[lane] : -2.f;
-      int bk = lane < kWaves ? wk[lane] : 0x7fffffff;
-#pragma unroll
-      for (int off = 8; off >= 1; off >>= 1) {
-        const float ov = __shfl_down(bv, off, 64);
-        const int ok = __shfl_down(bk, off, 64);
-        if (fps_better(ov, ok, bv, bk, bmask)) { bv = ov; bk = ok; }
-      }
-      if (G > 1) {
-        const int sl = (j & 1) * G;
-        if (lane == 0) {
-          __hip_atomic_store(cv + sl + w, bv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(ck + sl + w, bk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __threadfence();
-          __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-          const unsigned want = (unsigned)G * (unsigned)j;  // j-th meeting of the G members (m * G < 2^31: host-checked)
-          while (__hip_atomic_load(counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) __builtin_amdgcn_s_sleep(1);
-          __threadfence();
-        }
-        __threadfence();  // every lane: the candidate reads below stay behind lane 0's acquire
-        bv = -2.f;
-        bk = 0x7fffffff;
-        if (lane < G) {
-          bv = __hip_atomic_load(cv + sl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          bk = __hip_atomic_load(ck + sl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-          const float ov = __shfl_down(bv, off, 64);
-          const int ok = __shfl_down(bk, off, 64);
-          if (lane + off < 64 && fps_better(ov, ok, bv, bk, bmask)) { bv = ov; bk = ok; }
-        }
-      }
+      if (G > 1) c = fps_meet(c, j, G, w, bmask, cv, ck, counter);
       if (lane == 0) {
-        s_old = bk;
-        if (w == 0) out[j] = bk;
+        s_old = c.k;
+        if (w == 0) out[j] = c.k;
       }
     }
     __syncthreads();
@@ -243,17 +169,6 @@ __global__ __launch_bounds__(kThreads) void vp_fps_kernel(float4* __restrict__ p
 }
 
 // ---- 3. finish: one workgroup per view ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_min(double a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) a = fmin(a, __shfl_xor(a, off, 64));
-  return a;
-}
-__device__ __forceinline__ double wave_max(double a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) a = fmax(a, __shfl_xor(a, off, 64));
-  return a;
-}
-
 __global__ __launch_bounds__(kThreads) void vp_finish_kernel(
     const void* __restrict__ depth, int depth_f64, const uint8_t* __restrict__ rgb, const int32_t* __restrict__ sem,
     const int32_t* __restrict__ ins, const float* __restrict__ npcs, const double* __restrict__ Ks, int H, int W,
@@ -264,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void vp_finish_kernel(
   __shared__ int remap[kMaxInst];
   __shared__ int first[kMaxInst];
   __shared__ double red[6][kWaves];
-  const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int v = blockIdx.x, tid = threadIdx.x;
   if (status[v] != GPN_VIEW_OK) return;
   const int64_t HW = (int64_t)H * W, off = (int64_t)v * HW;
   const double* K = Ks + (int64_t)v * 9;
@@ -272,44 +187,16 @@ __global__ __launch_bounds__(kThreads) void vp_finish_kernel(
   const int32_t* fi = fps_idx + (int64_t)v * m;
   const int32_t* pix = pixel + off;
   for (int q = tid; q < kMaxInst; q += kThreads) { present[q] = 0; remap[q] = q; first[q] = 0x7fffffff; }
-  // min / max of the sampled float64 points (exact: the order of a min / max does not matter)
-  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int j = tid; j < m; j += kThreads) {
-    const int p = pix[fi[j]];
-    const int y = p / W, x = p - y * W;
-    const double z = depth_at(depth, depth_f64, off + p);
-    const double P[3] = {unproject(x, cx, z, fx), unproject(y, cy, z, fy), z};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { mn[c] = fmin(mn[c], P[c]); mx[c] = fmax(mx[c], P[c]); }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { mn[c] = wave_min(mn[c]); mx[c] = wave_max(mx[c]); }
-  if (lane == 0)
-    for (int c = 0; c < 3; ++c) { red[c][wave] = mn[c]; red[3 + c][wave] = mx[c]; }
-  __syncthreads();
-  double ctr[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double a = red[c][0], b = red[3 + c][0];
-    for (int q = 1; q < kWaves; ++q) { a = fmin(a, red[c][q]); b = fmax(b, red[3 + c][q]); }
-    ctr[c] = (b + a) / 2.0;  // :74 (max + min) / 2
-  }
-  __syncthreads();  // red is reused below
-  // r^2 = max of (dx^2 + dy^2) + dz^2 (:75; the square root is monotonic, so sqrt(max) = max(sqrt))
-  double r2 = -INFINITY;
-  for (int j = tid; j < m; j += kThreads) {
-    const int p = pix[fi[j]];
-    const int y = p / W, x = p - y * W;
-    const double z = depth_at(depth, depth_f64, off + p);
-    const double dx = unproject(x, cx, z, fx) - ctr[0], dy = unproject(y, cy, z, fy) - ctr[1], dz = z - ctr[2];
-    r2 = fmax(r2, (dx * dx + dy * dy) + dz * dz);
-  }
-  r2 = wave_max(r2);
-  if (lane == 0) red[0][wave] = r2;
-  __syncthreads();
-  r2 = red[0][0];
-  for (int q = 1; q < kWaves; ++q) r2 = fmax(r2, red[0][q]);
-  const double r = __dsqrt_rn(r2);
+  // centre (:74, (max + min) / 2) and radius (:75) of the sampled float64 points
+  double ctr[3], r;
+  ball_of_samples<kWaves>(
+      [&](int j, double* P) {
+        const int p = pix[fi[j]];
+        const int y = p / W, x = p - y * W;
+        const double z = depth_at(depth, depth_f64, off + p);
+        P[0] = unproject(x, cx, z, fx); P[1] = unproject(y, cy, z, fy); P[2] = z;
+      },
+      m, red, ctr, &r);
   // outputs; instance ids before the relabel loop
   int over = 0;
   for (int j = tid; j < m; j += kThreads) {
@@ -424,24 +311,11 @@ extern "C" int gpn_view_fps(float* points, int64_t n_bound, const int32_t* count
   unsigned* arrived = carve.take<unsigned>((size_t)V);
   GPN_CHECK_WS(carve);
   int G = fps_groups(V, max_groups);
-  if ((int64_t)m * G >= (int64_t)0x7fffffff) G = 1;
+  if (!fps_meetings_fit(m, G)) G = 1;
   float4* pts = reinterpret_cast<float4*>(points);
-  int nv = V, mm = m;
-  int64_t nb = n_bound;
-  if (G > 1) {
-    GPN_CHECK_HIP(hipMemsetAsync(arrived, 0, (size_t)V * sizeof(unsigned), stream));
-    // the counter wait runs only under a cooperative launch: the runtime starts the grid only when all of its workgroups can be
-    // resident at once, and refuses one that cannot be
-    void* args[] = {&pts, &nb, &counts, &status, &nv, &mm, &G, &idx, &cand_v, &cand_k, &arrived};
-    const unsigned grid = (unsigned)((V + 7) / 8 * 8 * G);
-    if (hipLaunchCooperativeKernel((const void*)vp_fps_kernel, dim3(grid), dim3(kThreads), args, 0, stream) == hipSuccess)
-      return GPN_OK;
-    (void)hipGetLastError();  // refused: the form without any inter-workgroup wait
-  }
-  hipLaunchKernelGGL(vp_fps_kernel, dim3((unsigned)((V + 7) / 8 * 8)), dim3(kThreads), 0, stream, pts, nb, counts, status, nv, mm,
-                     1, idx, cand_v, cand_k, arrived);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  void* args[] = {&pts, &n_bound, &counts, &status, &V, &m, &G, &idx, &cand_v, &cand_k, &arrived};
+  return fps_launch(__func__, (const void*)vp_fps_kernel, (const void*)vp_fps_kernel, (unsigned)((V + 7) / 8 * 8), &G, args, arrived,
+                    (size_t)V, stream);
 }
 
 extern "C" int gpn_view_finish(const void* depth, int depth_bytes, const uint8_t* rgb, const int32_t* sem, const int32_t* ins,

@@ -131,6 +131,19 @@ def _check_clouds(clouds: Sequence[torch.Tensor]):
     return clouds
 
 
+def _prepared_from_tables(got, m: int, offsets: List[int], source: torch.Tensor) -> PreparedClouds:
+    """the device tables of ``cloud_prepare`` / ``frame_prepare`` ([S, m] slots per cloud) as a ``PreparedClouds`` over ``source``"""
+    status = got["status"]
+    counts = torch.where(status == CLOUD_OK, got["counts"], torch.zeros_like(got["counts"]))
+    # (the live slots of the [S, m] tables, listed on the host from the counts it already holds: no second host read)
+    live = torch.arange(m)[None, :] < counts[:, None]
+    take = torch.nonzero(live.reshape(-1)).squeeze(1).to(source.device, non_blocking=True)
+    points = got["out"].reshape(counts.shape[0] * m, -1).index_select(0, take)
+    sample_rows = got["sample_rows"].reshape(-1).index_select(0, take).long()
+    table = dict(sample_rows=got["sample_rows"], counts=got["counts_dev"], status=got["status_dev"])
+    return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, source, table)
+
+
 def prepare_clouds(clouds: Sequence[torch.Tensor], num_points: int = 20000, max_groups: int = 0) -> PreparedClouds:
     """``clouds``: [N_i, C] float32 tensors, xyz first, any N_i (0 included); rows with a non-finite coordinate are skipped.  A cloud
     with more than ``num_points`` valid rows is sampled by FPS, a smaller one keeps every valid row; centre and radius of the ball
@@ -148,17 +161,7 @@ def prepare_clouds(clouds: Sequence[torch.Tensor], num_points: int = 20000, max_
         hip = backend.raw()
         if hip.name != "hip":
             raise RuntimeError("prepare_clouds on GPU tensors needs the HIP library as the operator backend")
-        got = hip.cloud_prepare(source, offsets, m, max_groups)
-        status = got["status"]
-        counts = torch.where(status == CLOUD_OK, got["counts"], torch.zeros_like(got["counts"]))
-        S = len(clouds)
-        # (the live slots of the [S, m] tables, listed on the host from the counts it already holds: no second host read)
-        live = torch.arange(m)[None, :] < counts[:, None]
-        take = torch.nonzero(live.reshape(-1)).squeeze(1).to(source.device, non_blocking=True)
-        points = got["out"].reshape(S * m, -1).index_select(0, take)
-        sample_rows = got["sample_rows"].reshape(-1).index_select(0, take).long()
-        table = dict(sample_rows=got["sample_rows"], counts=got["counts_dev"], status=got["status_dev"])
-        return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, source, table)
+        return _prepared_from_tables(hip.cloud_prepare(source, offsets, m, max_groups), m, offsets, source)
     parts = [_prepare_cloud_torch(c, m) for c in clouds]
     return PreparedClouds(torch.cat([p[1] for p in parts]), torch.tensor([p[1].shape[0] for p in parts], dtype=torch.int64),
                           torch.cat([p[2] for p in parts]), torch.stack([p[3] for p in parts]),
@@ -286,14 +289,7 @@ def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, de
             raise RuntimeError("prepare_frames on GPU tensors needs the HIP library as the operator backend")
         got = hip.frame_prepare(depth, rgb, K.to(depth.device, non_blocking=True), m, cap, seeds, keep=keep, depth_scale=depth_scale, flip=flip,
                                 hash_bits=hash_bits, max_groups=max_groups)
-        status = got["status"]
-        counts = torch.where(status == CLOUD_OK, got["counts"], torch.zeros_like(got["counts"]))
-        live = torch.arange(m)[None, :] < counts[:, None]
-        take = torch.nonzero(live.reshape(-1)).squeeze(1).to(depth.device, non_blocking=True)
-        points = got["out"].reshape(V * m, -1).index_select(0, take)
-        sample_rows = got["sample_rows"].reshape(-1).index_select(0, take).long()
-        table = dict(sample_rows=got["sample_rows"], counts=got["counts_dev"], status=got["status_dev"])
-        return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, got["rows"], table)
+        return _prepared_from_tables(got, m, offsets, got["rows"])
     d = depth.numpy()
     rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), K.numpy(),
                                      None if keep is None else keep.numpy(), depth_scale, flip)
@@ -505,6 +501,19 @@ MASK_FIELDS = ("kept", "n_points", "label", "score", "valid", "scale", "rotation
                "member_offsets", "member_rows", "member_npcs")
 
 
+def _rows_through_nearest(prep: PreparedClouds, net_off: List[int], *per_sample: torch.Tensor) -> List[torch.Tensor]:
+    """every row of the caller's clouds through its nearest sampled point: for each tensor over the network's rows (``net_off``: the
+    clouds' first rows there) the tensor over the caller's rows; -1 (integers) or 0 (floats) on rows that have no sample"""
+    dev = prep.source.device
+    nn = nearest_samples(prep)
+    first = torch.repeat_interleave(torch.tensor(net_off[:-1], dtype=torch.int64).to(dev),
+                                    torch.tensor([b - a for a, b in zip(prep.offsets[:-1], prep.offsets[1:])]).to(dev),
+                                    output_size=prep.offsets[-1])
+    hit = nn >= 0
+    g = (first + nn).clamp(min=0, max=max(net_off[-1] - 1, 0))
+    return [torch.where(hit.reshape(-1, *[1] * (v.dim() - 1)), v[g], 0.0 if v.is_floating_point() else -1) for v in per_sample]
+
+
 class PartPredictor:
     """``predict(clouds)``: raw clouds in, per cloud the parts of EVERY row and one 9-DoF box per part in the caller's frame.
     ``picks``: the RANSAC draws of the box fits - None (drawn from numpy's global generator), a tensor [kept proposals,
@@ -558,16 +567,7 @@ class PartPredictor:
             # (scene k of the network's batch is the k-th OK cloud; the clouds that are not OK own no rows)
             pred = _scene_predictions(kept, [net_off[s] for s in ok] + [n_net], picks, self.max_iters)
             ins, npcs = pred.ins_map.long() - 1, pred.npcs_map
-        # every row of the caller's clouds through its nearest sampled point
-        nn = nearest_samples(prep)
-        first = torch.repeat_interleave(torch.tensor(net_off[:-1], dtype=torch.int64).to(dev),
-                                        torch.tensor([b - a for a, b in zip(prep.offsets[:-1], prep.offsets[1:])]).to(dev),
-                                        output_size=prep.offsets[-1])
-        hit = nn >= 0
-        g = (first + nn).clamp(min=0, max=max(n_net - 1, 0))
-        sem_all = torch.where(hit, sem[g], -1)
-        ins_all = torch.where(hit, ins[g], -1)
-        npcs_all = torch.where(hit[:, None], npcs[g], torch.zeros_like(npcs[g]))
+        sem_all, ins_all, npcs_all = _rows_through_nearest(prep, net_off, sem, ins, npcs)
         if kept is not None:
             P = kept.score_preds.shape[0]
             prop_scene = kept.batch_indices.index_select(0, kept.proposal_offsets[:-1].long()).long()  # [P], in the OK clouds' numbering
@@ -600,17 +600,6 @@ class PartPredictor:
             o.bbox = o.bbox_normalised * sc[0] + sc[1:]
             o.box_proposal = local[pred.box_proposal.index_select(0, boxes)]
         return out
-
-
-    def _rows_sem(self, prep: PreparedClouds, sem: torch.Tensor, net_off: List[int]) -> torch.Tensor:
-        """the part class of every row of the caller's clouds through its nearest sampled point (-1 on invalid rows)"""
-        dev = prep.source.device
-        nn = nearest_samples(prep)
-        first = torch.repeat_interleave(torch.tensor(net_off[:-1], dtype=torch.int64).to(dev),
-                                        torch.tensor([b - a for a, b in zip(prep.offsets[:-1], prep.offsets[1:])]).to(dev),
-                                        output_size=prep.offsets[-1])
-        g = (first + nn).clamp(min=0, max=max(net_off[-1] - 1, 0))
-        return torch.where(nn >= 0, sem[g], -1)
 
     @torch.no_grad()
     def predict_with_masks(self, clouds: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], labels: Sequence[torch.Tensor],
@@ -663,7 +652,7 @@ class PartPredictor:
         _, sem_seg, props, _ = model.forward_with_masks(pcs, [masks[s] for s in ok], [labels[s] for s in ok], min_points=min_points,
                                                         sample_rows=prep.sample_rows)
         sem = sem_seg.sem_preds.long()
-        sem_all = self._rows_sem(prep, sem, net_off)
+        sem_all, = _rows_through_nearest(prep, net_off, sem)
         # per mask of the batch (the OK clouds' masks, concatenated): scattered from the kept ones
         gstart = [0]
         for s in ok:

@@ -948,6 +948,52 @@ def test_fps_big_cloud_shared_by_workgroups(H, cuda):
     assert rc == 0 and np.array_equal(idx.cpu().numpy(), got)
 
 
+def fps_batch_clouds(n=65536):
+    """[3, n, 3]: a random cloud, a 0.25-spaced grid (many distances exactly equal), n copies of one point (all distances equal)"""
+    rng = np.random.default_rng(11)
+    side = int(np.ceil(n ** (1 / 3)))
+    grid = np.stack(np.meshgrid(*[np.arange(side, dtype=np.float32)] * 3, indexing="ij"), -1).reshape(-1, 3)[:n] * 0.25
+    same = np.tile(np.array([[0.5, -1.25, 2.0]], dtype=np.float32), (n, 1))
+    return np.stack([rng.random((n, 3)).astype(np.float32), grid, same])
+
+
+@pytest.mark.gpu
+def test_fps_batch_of_clouds_shared_by_workgroups(cuda):
+    """A batch of clouds of 65536 points, the smallest size at which gpn_pn2_furthest_point_sampling_ws shares a cloud between
+    workgroups: one kernel serves (cloud, member) pairs, so the members of three clouds meet at three counters at once.  The
+    samples are those of the plain entry point (one workgroup per cloud, the same kernel without meetings) and of the oracle;
+    a second call on the same workspace gives them again (the arrival counters are zeroed by every call).  What it cannot see:
+    a non-empty workspace says that the host chose G > 1, not that the cooperative launch was accepted - had the runtime refused
+    it, the library would have run one workgroup per cloud and all three runs would have taken that form (as in
+    test_fps_big_cloud_shared_by_workgroups; the library has no way to observe the fallback)."""
+    from gapartnet_amd import _C
+    L = _C.lib()
+    b, n, m = 3, 65536, 40
+    xyz = fps_batch_clouds(n)
+    want = O.pn2_furthest_point_sampling(xyz, m)
+    t = torch.from_numpy(xyz).to(cuda)
+    vp, stream = ctypes.c_void_p, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ws_bytes = L.gpn_pn2_furthest_point_sampling_ws_bytes(b, n)
+    assert ws_bytes > 0  # (several workgroups per cloud)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=cuda)
+
+    def run(shared):
+        temp = torch.full((b, n), 1e10, dtype=torch.float32, device=cuda)
+        idx = torch.full((b, m), -1, dtype=torch.int32, device=cuda)
+        args = [b, n, m, vp(t.data_ptr()), vp(temp.data_ptr()), vp(idx.data_ptr())]
+        if shared:
+            rc = L.gpn_pn2_furthest_point_sampling_ws(*args, vp(ws.data_ptr()), ctypes.c_size_t(ws_bytes), stream)
+        else:
+            rc = L.gpn_pn2_furthest_point_sampling(*args, stream)
+        assert rc == 0
+        return idx.cpu().numpy()
+
+    first, again, plain = run(True), run(True), run(False)
+    assert np.array_equal(first, want)
+    assert np.array_equal(again, want)
+    assert np.array_equal(plain, want)
+
+
 def test_copy_many_segments_in_one_launch(H, cuda):
     """gpn_copy_many (section O): any number of fp32 segments - more than one launch's 96, empty ones, odd lengths - land
     in their destinations; used by FusedAdam for the gradients autograd allocates afresh every step"""
