@@ -1729,6 +1729,71 @@ def frame_prepare(depth, rgb, K, m, cap, seeds, keep=None, depth_scale=1.0, flip
     return got
 
 
+# ---------------------------------------------------------------------------------------------------- JE (joint estimation)
+JOINT_TYPES = {"revolute": 0, "prismatic": 1}
+
+
+def joint_sample(pc1, pc2, off1, off2, picks1, picks2, k1, k2):
+    """pc1 [n1,3], pc2 [n2,3] f64 (pair b = rows off[b]:off[b+1], off [B+1] i64), picks [B,K] i64 (rows inside the segment), k [B]
+    i32 live picks -> (X [B,K,3], Y [B,K,3], norm [B,4] = (S, Mx, My, Mz)), include/gpn.h section JE"""
+    dev = _dev(pc1, pc2, off1, off2, picks1, picks2, k1, k2)
+    f64 = torch.float64
+    pc1, pc2 = _c(pc1, f64), _c(pc2, f64)
+    off1, off2, picks1, picks2 = (_c(t, torch.int64) for t in (off1, off2, picks1, picks2))
+    k1, k2 = _c(k1, torch.int32), _c(k2, torch.int32)
+    B, K = (int(v) for v in picks1.shape)
+    if tuple(picks2.shape) != (B, K) or off1.numel() != B + 1 or off2.numel() != B + 1 or k1.numel() != B or k2.numel() != B:
+        raise _C.GpnError("joint_sample: picks [B,K] twice, offsets [B+1] twice, k [B] twice")
+    X = torch.empty((B, K, 3), dtype=f64, device=dev)
+    Y = torch.empty((B, K, 3), dtype=f64, device=dev)
+    norm = torch.empty((B, 4), dtype=f64, device=dev)
+    check(_C.lib().gpn_joint_sample(ptr(pc1), ptr(pc2), ptr(off1), ptr(off2), ptr(picks1), ptr(picks2), ptr(k1), ptr(k2), i64(B),
+                                    i32(K), ptr(X), ptr(Y), ptr(norm), _stream()), "gpn_joint_sample")
+    return X, Y, norm
+
+
+def cpd_rigid(X, Y, nx, ny, max_iterations=100, tolerance=1e-3, w=0.0, scale=True, want_trace=False):
+    """CPD rigid registration of Y [B,K,3] (ny[b] rows) onto X [B,K,3] (nx[b] rows), the whole EM loop of every pair in one launch
+    (section JE) -> dict: s [B], R [B,3,3], t [B,3] (TY = s Y R + t), sigma2, q, diff [B], iterations [B] i32, and sigma2_trace
+    [B,max_iterations] when asked for"""
+    dev = _dev(X, Y, nx, ny)
+    f64 = torch.float64
+    X, Y, nx, ny = _c(X, f64), _c(Y, f64), _c(nx, torch.int32), _c(ny, torch.int32)
+    if X.dim() != 3 or X.shape[2] != 3 or Y.shape != X.shape or nx.numel() != X.shape[0] or ny.numel() != X.shape[0]:
+        raise _C.GpnError("cpd_rigid: X and Y [B,K,3], nx and ny [B]")
+    B, K = int(X.shape[0]), int(X.shape[1])
+    out = {"s": torch.empty(B, dtype=f64, device=dev), "R": torch.empty(B, 3, 3, dtype=f64, device=dev),
+           "t": torch.empty(B, 3, dtype=f64, device=dev), "sigma2": torch.empty(B, dtype=f64, device=dev),
+           "q": torch.empty(B, dtype=f64, device=dev), "diff": torch.empty(B, dtype=f64, device=dev),
+           "iterations": torch.empty(B, dtype=torch.int32, device=dev)}
+    if want_trace:
+        out["sigma2_trace"] = torch.empty(B, int(max_iterations), dtype=f64, device=dev)
+    dbl = _C.ctypes.c_double
+    check(_C.lib().gpn_cpd_rigid(ptr(X), ptr(Y), ptr(nx), ptr(ny), i64(B), i32(K), i32(int(max_iterations)), dbl(float(tolerance)),
+                                 dbl(float(w)), i32(1 if scale else 0), ptr(out["s"]), ptr(out["R"]), ptr(out["t"]),
+                                 ptr(out["sigma2"]), ptr(out["q"]), ptr(out["diff"]), ptr(out["iterations"]),
+                                 ptr(out.get("sigma2_trace")), _stream()), "gpn_cpd_rigid")
+    return out
+
+
+def joint_from_rigid(rotation, translation, norm, joint_type="revolute"):
+    """rotation [G,3,3], translation [G,3], norm [G,4] f64 -> (axis [G,3], pivot [G,3], angle [G]), section JE"""
+    dev = _dev(rotation, translation, norm)
+    f64 = torch.float64
+    rotation, translation, norm = _c(rotation, f64), _c(translation, f64), _c(norm, f64)
+    G = int(translation.shape[0])
+    if rotation.numel() != G * 9 or translation.numel() != G * 3 or norm.numel() != G * 4:
+        raise _C.GpnError("joint_from_rigid: rotation [G,3,3], translation [G,3], norm [G,4]")
+    if joint_type not in JOINT_TYPES:
+        raise _C.GpnError(f"joint_from_rigid: joint_type is 'revolute' or 'prismatic', got {joint_type!r}")
+    axis = torch.empty((G, 3), dtype=f64, device=dev)
+    pivot = torch.empty((G, 3), dtype=f64, device=dev)
+    angle = torch.empty((G,), dtype=f64, device=dev)
+    check(_C.lib().gpn_joint_from_rigid(ptr(rotation), ptr(translation), ptr(norm), i64(G), i32(JOINT_TYPES[joint_type]), ptr(axis),
+                                        ptr(pivot), ptr(angle), _stream()), "gpn_joint_from_rigid")
+    return axis, pivot, angle
+
+
 # ---------------------------------------------------------------------------------------------------- VS (test-time rendering)
 VISU_RGB, VISU_LABEL, VISU_LABEL_MOD20, VISU_LABEL_MOD19P1, VISU_BLANK = 0, 1, 2, 3, 4
 VISU_MAX_LAYERS = 16

@@ -982,6 +982,53 @@ int gpn_pose_fit(const double* xyz, const double* npcs, const int64_t* offsets, 
                  size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * JE - joint estimation: the axis direction, a point on the axis and the angle of the joint a part moved about, from two
+ * observations of the part (the reference's estimate_joint_angle, structure/gapartnet.py:819-963), for a batch of B pairs.
+ * Three launches, float64 like the reference, no host read between them, no float atomics: every reduction has a fixed shape
+ * (per-thread strided sums, a shuffle tree per wave, the waves in order), so results are bit-reproducible and a pair's result
+ * does not depend on the other pairs of the batch.  K <= GPN_JOINT_MAX_K.
+ * gpn_joint_sample (:836-845): pc1 [n1_total,3], pc2 [n2_total,3] f64, pair b = rows off[b]:off[b+1] (off1, off2 [B+1] i64);
+ *   picks1, picks2 [B,K] i64 = rows INSIDE the pair's segment (the reference's random.sample; drawn by the caller:
+ *   gapartnet_amd.misc.joint_fitting.draw_joint_picks); k1, k2 [B] i32 = live picks of the row.  M = mean of the pair's pc2
+ *   rows, S = the largest per-axis extent max(pc2 - M) - min(pc2 - M), X = (pc1[picks1] - M) / S, Y = (pc2[picks2] - M) / S (a
+ *   division).  X, Y [B,K,3], rows beyond k zero; norm [B,4] = (S, Mx, My, Mz).  An empty pc2 segment gives NaN; a pick outside
+ *   its segment gives a NaN row and reads nothing.
+ * gpn_cpd_rigid: Coherent Point Drift rigid registration (Myronenko & Song 2010, as pycpd.RigidRegistration runs it with its
+ *   defaults) of the moving set Y [B,K,3] (M = ny[b] rows) onto the fixed set X [B,K,3] (N = nx[b] rows), one workgroup a pair,
+ *   the whole EM loop in the launch.  Row convention: TY = s Y R + t.
+ *   Start: R = I, t = 0, s = 1, sigma2 = sum_mn |x_n - y_m|^2 / (3 M N), q = diff = inf.
+ *   While iteration < max_iterations and diff > tolerance (a NaN diff ends the loop):
+ *     E: P_mn = exp(-|x_n - TY_m|^2 / (2 sigma2)) / den_n, den_n = max(sum_m exp(..), DBL_EPSILON) + c,
+ *        c = (2 pi sigma2)^(3/2) w / (1 - w) M / N (no column maximum is subtracted first).
+ *     M: Np = sum P, muX = sum_n Pt1_n x_n / Np, muY = sum_m P1_m y_m / Np, A = sum_mn P_mn (x_n - muX)(y_m - muY)^T = U S V^T,
+ *        R = (U diag(1, 1, det(U V^T)) V^T)^T, YPY = sum_m P1_m |y_m - muY|^2, s = tr(A R) / YPY (1 when scale == 0),
+ *        t = muX - s R^T muY, TY = s Y R + t.
+ *     Variance: xPx = sum_n Pt1_n |x_n - muX|^2, q' = (xPx - 2 s tr(A R) + s^2 YPY) / (2 sigma2) + 1.5 Np ln sigma2,
+ *        diff = |q' - q|, sigma2 = (xPx - s tr(A R)) / (3 Np), replaced by tolerance / 10 when <= 0.
+ *   The M x N matrix is never stored: every sum above is a sum over columns n of per-column sums over m.
+ *   Outputs: s [B], R [B,3,3], t [B,3], sigma2 [B], q [B], diff [B], iterations [B] i32, and sigma2_trace [B,max_iterations]
+ *   or NULL = sigma2 at the end of every iteration run, NaN after the last.  A pair with nx or ny outside 1 .. K writes NaN
+ *   and iterations = 0.  0 <= w < 1.
+ * gpn_joint_from_rigid (:850-856 = :867-873) for G transforms: rotation [G,3,3], translation [G,3], norm [G,4] ->
+ *   axis [G,3], pivot [G,3], angle [G].  GPN_JOINT_REVOLUTE: the rotation vector through the unit quaternion with w >= 0 as
+ *   scipy's Rotation.from_matrix(..).as_rotvec(); angle = |rotvec|, axis = rotvec / angle (NaN at angle 0, as in the reference),
+ *   r = the matrix of the rotation vector (pi/2 - angle/2) axis, pivot = (t r / 2) / sin(angle / 2) * S + M.
+ *   GPN_JOINT_PRISMATIC (an extension: the reference takes joint_type and ignores it): axis = t / |t|, angle = |t| S (the
+ *   displacement), pivot = M.
+ * ================================================================================================ */
+#define GPN_JOINT_MAX_K 4096
+#define GPN_JOINT_REVOLUTE 0
+#define GPN_JOINT_PRISMATIC 1
+int gpn_joint_sample(const double* pc1, const double* pc2, const int64_t* off1, const int64_t* off2, const int64_t* picks1,
+                     const int64_t* picks2, const int32_t* k1, const int32_t* k2, int64_t B, int K, double* X, double* Y,
+                     double* norm, gpn_stream_t stream);
+int gpn_cpd_rigid(const double* X, const double* Y, const int32_t* nx, const int32_t* ny, int64_t B, int K, int max_iterations,
+                  double tolerance, double w, int scale, double* s, double* R, double* t, double* sigma2, double* q, double* diff,
+                  int32_t* iterations, double* sigma2_trace, gpn_stream_t stream);
+int gpn_joint_from_rigid(const double* rotation, const double* translation, const double* norm, int64_t G, int joint_type,
+                         double* axis, double* pivot, double* angle, gpn_stream_t stream);
+
+/* ================================================================================================
  * VS - test-time part predictions and the 3 x 4 panel of images per sampled scene (the reference's on_test_epoch_end,
  * network/model.py:930-999, misc/visu.py, misc/visu_util.py).  Every "the last writer of the loop wins" of the reference is an
  * integer atomicMax over the writer's position and a resolve pass: results are bit-reproducible and never depend on timing; no
