@@ -31,35 +31,6 @@ constexpr int kCpdTile = kCpdThreads;     // rows of the moving set staged per p
 constexpr int kCpdSums = 18;              // Np | sum P x [3] | sum P y [3] | sum P x y^T [9] | sum P |x|^2 | sum P |y|^2
 constexpr int kMaxWaves = kCpdThreads / 64;
 
-struct SumOp {
-  __device__ __forceinline__ double operator()(double a, double b) const { return a + b; }
-};
-struct MaxOp {
-  __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); }
-};
-
-// fixed-shape reduction of NV doubles per thread over the workgroup (blockDim.x a multiple of 64): a shuffle tree inside every
-// wave, then the waves' partials in wave order; the result in every thread.  Every thread of the workgroup must call it.
-template <int NV, typename Op>
-__device__ __forceinline__ void block_reduce(double (&v)[NV], double* red /* [kMaxWaves][NV] */, Op op) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double x = v[q];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = op(x, __shfl_down(x, off, 64));
-    if (lane == 0) red[wave * NV + q] = x;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double acc = red[q];
-    for (int w = 1; w < waves; ++w) acc = op(acc, red[w * NV + q]);
-    v[q] = acc;
-  }
-  __syncthreads();
-}
-
 // ---- gpn_joint_sample ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSampleThreads) void joint_sample_kernel(
     const double* __restrict__ pc1, const double* __restrict__ pc2, const int64_t* __restrict__ off1,

@@ -1,5 +1,5 @@
-// pose_math.h - the 3x3 float64 matrix helpers shared by the pose kernels (pose.hip) and the joint kernels (joint.hip): the matrix
-// type, its determinant and the one-sided Jacobi SVD.  Device code only; every function is internal to the including file.
+// pose_math.h - the float64 helpers shared by the pose kernels (pose.hip), the joint kernels (joint.hip) and the pose-evaluation
+// kernels (poseeval.hip): the 3x3 matrix type, its determinant, the one-sided Jacobi SVD and the fixed-shape workgroup reduction.  Device code only; every function is internal to the including file.
 #pragma once
 #include "gpn_common.h"
 
@@ -95,6 +95,35 @@ __device__ void svd3(const M3& A, M3& U, double (&S)[3], M3& V) {
   for (int k = 0; k < 3; ++k)
 #pragma unroll
     for (int r = 0; r < 3; ++r) U.a[r][k] = u[k][r];
+}
+
+struct SumOp {
+  __device__ __forceinline__ double operator()(double a, double b) const { return a + b; }
+};
+struct MaxOp {
+  __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); }
+};
+
+// fixed-shape reduction of NV doubles per thread over the workgroup (blockDim.x a multiple of 64): a shuffle tree inside every
+// wave, then the waves' partials in wave order; the result in every thread.  Every thread of the workgroup must call it.
+template <int NV, typename Op>
+__device__ __forceinline__ void block_reduce(double (&v)[NV], double* red /* [waves][NV] */, Op op) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    double x = v[q];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = op(x, __shfl_down(x, off, 64));
+    if (lane == 0) red[wave * NV + q] = x;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    double acc = red[q];
+    for (int w = 1; w < waves; ++w) acc = op(acc, red[w * NV + q]);
+    v[q] = acc;
+  }
+  __syncthreads();
 }
 
 }  // namespace

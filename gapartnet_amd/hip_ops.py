@@ -1794,6 +1794,61 @@ def joint_from_rigid(rotation, translation, norm, joint_type="revolute"):
     return axis, pivot, angle
 
 
+# ---------------------------------------------------------------------------------------------------- PE (pose evaluation)
+def pose_gt_fit(xyz, npcs, slot, scene_offsets, W):
+    """xyz, npcs [N,3] f32, slot [N] i32 (scene * W + instance id, negative = none), scene_offsets [S+1] i64 -> dict per slot
+    [S*W]: count i64, valid u8, scale, rotation [.,3,3], translation [.,3], half [.,3], bbox [.,8,3] f64 (section PE)"""
+    dev = _dev(xyz, npcs, slot, scene_offsets)
+    f64 = torch.float64
+    xyz, npcs, slot, scene_offsets = _c(xyz, torch.float32), _c(npcs, torch.float32), _c(slot, torch.int32), _c(scene_offsets, torch.int64)
+    N, S, W = int(slot.numel()), int(scene_offsets.numel()) - 1, int(W)
+    if xyz.numel() != N * 3 or npcs.numel() != N * 3 or S < 0 or W < 0:
+        raise _C.GpnError("pose_gt_fit: xyz and npcs [N,3], slot [N], scene_offsets [S+1], W >= 0")
+    G = S * W
+    out = {"count": torch.empty(G, dtype=torch.int64, device=dev), "valid": torch.empty(G, dtype=torch.uint8, device=dev),
+           "scale": torch.empty(G, dtype=f64, device=dev), "rotation": torch.empty(G, 3, 3, dtype=f64, device=dev),
+           "translation": torch.empty(G, 3, dtype=f64, device=dev), "half": torch.empty(G, 3, dtype=f64, device=dev),
+           "bbox": torch.empty(G, 8, 3, dtype=f64, device=dev)}
+    check(_C.lib().gpn_pose_gt_fit(ptr(xyz), ptr(npcs), ptr(slot), ptr(scene_offsets), i64(N), i32(S), i32(W), ptr(out["count"]),
+                                   ptr(out["valid"]), ptr(out["scale"]), ptr(out["rotation"]), ptr(out["translation"]),
+                                   ptr(out["half"]), ptr(out["bbox"]), _stream()), "gpn_pose_gt_fit")
+    return out
+
+
+def box_iou_3d(a, b):
+    """exact IoU of P pairs of oriented boxes a, b [P,8,3] f64 (corner order of gpn_pose_fit's bbox) -> [P] f64; NaN for a
+    non-finite corner or a zero extent (section PE, with the tie rule of the clipping)"""
+    dev = _dev(a, b)
+    a, b = _c(a, torch.float64), _c(b, torch.float64)
+    if a.dim() != 3 or tuple(a.shape[1:]) != (8, 3) or a.shape != b.shape:
+        raise _C.GpnError("box_iou_3d: a and b [P,8,3]")
+    P = int(a.shape[0])
+    iou = torch.empty(P, dtype=torch.float64, device=dev)
+    check(_C.lib().gpn_box_iou_3d(ptr(a), ptr(b), i64(P), ptr(iou), _stream()), "gpn_box_iou_3d")
+    return iou
+
+
+def pose_pair_errors(pred, gt, sym_type, sym_table, sym_start, sym_count):
+    """pred, gt = (scale [P], rotation [P,3,3], translation [P,3], half [P,3]) f64, sym_type [P] i32, sym_table [K,3,3] f64 with
+    sym_start, sym_count [T] i32 -> dict: re_deg, te, se, iou [P] f64, k_re, k_iou [P] i32 (section PE)"""
+    f64, i32t = torch.float64, torch.int32
+    dev = _dev(*pred, *gt, sym_type, sym_table, sym_start, sym_count)
+    pred, gt = [_c(t, f64) for t in pred], [_c(t, f64) for t in gt]
+    sym_type, sym_table, sym_start, sym_count = _c(sym_type, i32t), _c(sym_table, f64), _c(sym_start, i32t), _c(sym_count, i32t)
+    P, K, T = int(sym_type.numel()), int(sym_table.shape[0]), int(sym_start.numel())
+    for side in (pred, gt):
+        if [int(t.numel()) for t in side] != [P, P * 9, P * 3, P * 3]:
+            raise _C.GpnError("pose_pair_errors: scale [P], rotation [P,3,3], translation [P,3], half [P,3] on both sides")
+    if sym_table.numel() != K * 9 or sym_count.numel() != T:
+        raise _C.GpnError("pose_pair_errors: sym_table [K,3,3], sym_start and sym_count [T]")
+    out = {k: torch.empty(P, dtype=f64, device=dev) for k in ("re_deg", "te", "se", "iou")}
+    out["k_re"], out["k_iou"] = torch.empty(P, dtype=i32t, device=dev), torch.empty(P, dtype=i32t, device=dev)
+    check(_C.lib().gpn_pose_pair_errors(*(ptr(t) for t in pred), *(ptr(t) for t in gt), ptr(sym_type), i64(P), ptr(sym_table), i32(K),
+                                        ptr(sym_start), ptr(sym_count), i32(T), ptr(out["re_deg"]), ptr(out["k_re"]), ptr(out["te"]),
+                                        ptr(out["se"]), ptr(out["iou"]), ptr(out["k_iou"]), _stream()), "gpn_pose_pair_errors")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- VS (test-time rendering)
 VISU_RGB, VISU_LABEL, VISU_LABEL_MOD20, VISU_LABEL_MOD19P1, VISU_BLANK = 0, 1, 2, 3, 4
 VISU_MAX_LAYERS = 16

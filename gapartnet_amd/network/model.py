@@ -15,7 +15,7 @@ Pipeline of one step (model.py:466-659):
 """
 import functools
 import os
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -92,11 +92,21 @@ class GAPartNet(LightningModule):
         # points.reshape(-1, 6, N), a reinterpretation (not a transpose) that its checkpoints were trained with - equal-sized
         # scenes only; "points" = every point its own six values, ragged batches allowed
         pointnet_input_layout: str = "reference",
+        # not in the reference (whose "# pose estimation" is a stub): True = test epochs also log the pose metrics of the matched
+        # part poses, {split}/pose_Re .. pose_pairs (gapartnet_amd/misc/pose_metrics.py).  Off: nothing changes.
+        evaluate_pose: bool = False,
+        # the RANSAC draws of those metrics' predicted poses: a callable sizes -> [Q,H,5] (pose_fitting_batched.draw_picks'
+        # contract); None = draw_picks, numpy's global generator.  (It is saved with the hyper-parameters: picklable if checkpoints
+        # are written.)
+        pose_picks: Optional[Callable] = None,
     ):
         super().__init__()
         self.save_hyperparameters()
         self.validation_step_outputs = []
         self._visualize_outputs = []  # per loader, per test step: what the rendering of on_test_epoch_end needs (visualize only)
+        self.evaluate_pose = bool(evaluate_pose)
+        self.pose_picks = pose_picks
+        self._pose_evaluators = {}  # loader index -> PoseEvaluator of the running test epoch (evaluate_pose only)
 
         self.in_channels = in_channels
         self.num_part_classes = num_part_classes
@@ -1079,6 +1089,8 @@ class GAPartNet(LightningModule):
         return pc_ids, sem_seg, kept
 
     def test_step(self, point_clouds, batch_idx: int, dataloader_idx: int = 0):
+        if self.evaluate_pose:  # (the pose metrics read the collated batch's ground truth: collate here, the step takes it as it is)
+            point_clouds = self._collate(point_clouds)
         pc_ids, sem_seg, proposals, _ = self._training_or_validation_step(
             point_clouds, batch_idx, ["val", "intra", "inter"][dataloader_idx], want_npcs_preds=True)
         kept = None
@@ -1091,6 +1103,14 @@ class GAPartNet(LightningModule):
                              num_points_per_instance=p.num_points_per_instance, sorted_indices=p.sorted_indices,
                              npcs_preds=p.npcs_preds, npcs_valid_mask=p.npcs_valid_mask)
         self._stash(dataloader_idx, (pc_ids, sem_seg, kept))
+        if self.evaluate_pose:
+            # the batch's pairs are evaluated here (two host reads) and only their [Q,7] rows stay until the epoch ends: keeping the
+            # batches themselves in a side list would hold every test batch's points, NPCS and proposals on the device
+            from ..misc.pose_metrics import PoseEvaluator
+            if dataloader_idx not in self._pose_evaluators:
+                self._pose_evaluators[dataloader_idx] = PoseEvaluator(
+                    self.num_part_classes, self.symmetry_indices, **({} if self.pose_picks is None else {"picks": self.pose_picks}))
+            self._pose_evaluators[dataloader_idx].update(kept, point_clouds)
         if self.visualize_cfg.get("visualize", False):
             # what the rendering of on_test_epoch_end needs beyond the reference's 3-tuple: the scenes' real row counts and the
             # proposal fields the kept Instances does not carry (a side list: the returned tuple stays the reference's)
@@ -1201,9 +1221,25 @@ class GAPartNet(LightningModule):
     def on_validation_epoch_end(self):
         self._epoch_end_metrics()
 
+    def _pose_metrics(self) -> None:
+        """{split}/pose_Re [deg], pose_Te, pose_Se, pose_mIoU, pose_A5, pose_A10 [%] (means over the classes that have pairs; a NaN
+        is not logged) and pose_pairs of the matched part poses (misc/pose_metrics.py); Te and Se in the network's ball frame"""
+        for idx, evaluator in sorted(self._pose_evaluators.items()):
+            split = _SPLITS[idx]
+            result = evaluator.compute()
+            log = functools.partial(self.log, batch_size=max(evaluator.num_scenes, 1), on_epoch=True, logger=True, sync_dist=True,
+                                    prog_bar=False)
+            for key, value in result["mean"].items():
+                if np.isfinite(value):
+                    log(f"{split}/pose_{key}", value * (100.0 if key[0] == "A" or key == "mIoU" else 1.0))
+            log(f"{split}/pose_pairs", float(result["total_pairs"]))
+        self._pose_evaluators.clear()
+
     def on_test_epoch_end(self):
         if self.visualize_cfg.get("visualize", False):
             self._render_test_outputs()
+        if self.evaluate_pose:
+            self._pose_metrics()
         self._epoch_end_metrics()
 
     def configure_optimizers(self):

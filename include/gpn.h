@@ -1029,6 +1029,53 @@ int gpn_joint_from_rigid(const double* rotation, const double* translation, cons
                          double* axis, double* pivot, double* angle, gpn_stream_t stream);
 
 /* ================================================================================================
+ * PE - pose evaluation: is an estimated part pose right?  The ground-truth pose of every instance, the exact IoU of two oriented
+ * boxes, and the errors of matched (prediction, ground truth) pairs under the part's symmetry group: what the GAPartNet paper
+ * reports for its second task (R_e, T_e, S_e, 3D IoU).  The reference has no counterpart (on_test_epoch_end ends at a
+ * commented-out "# pose estimation").  Float64 arithmetic, no float atomics, no host read; every reduction has a fixed shape, so
+ * results are bit-equal from run to run and one item's result does not depend on the other items of the call.  Counts of 0
+ * are valid calls that launch nothing.  Boxes are 8 corners in the order (---, +--, -+-, --+, ++-, +-+, -++, +++) of
+ * gpn_pose_fit's bbox.
+ * gpn_pose_gt_fit: the similarity xyz ~ npcs @ (s R) + t (row vectors, as gpn_pose_fit) of every ground-truth instance by plain
+ *   Umeyama over ALL its points.  xyz, npcs [N,3] f32; slot [N] i32 = scene * W + the point's instance id in its scene, negative =
+ *   none (a slot outside its own scene's range is ignored as well); scene_offsets [S+1] i64 on the device.  One workgroup per slot
+ *   walks its scene's rows twice (means, then centred moments); the k-th point of an instance always goes to the same thread in the
+ *   same turn, whatever lies between the instance's points.  Outputs per slot [S*W]: count i64, valid u8, scale, rotation [3,3],
+ *   translation [3], half [3] = max |npcs| per axis over the instance (the observed extent, as gpn_pose_fit's box has it), bbox
+ *   [8,3] = (signs * half * s) @ R + t.  valid = 0, with NaN in every float output, for fewer than 3 points, for an NPCS covariance
+ *   whose second singular value is below 1e-9 x its first (collinear points) and for non-finite input; a planar instance (rank 2)
+ *   is valid: the reflection rule of Umeyama fixes the third axis.
+ * gpn_box_iou_3d: IoU of P pairs a [P,8,3], b [P,8,3] f64.  Centre = the corners' mean, axes and half extents from the edges
+ *   corner 1, 2, 3 - corner 0.  Each of the 12 faces (6 of a, then 6 of b; face 2 i + 0/1 = the -/+ side of axis i) is clipped by
+ *   the 6 half-spaces of the other box (Sutherland-Hodgman, <= 10 vertices) and contributes area * height / 3 with the height from
+ *   a's centre along the face's outward normal; intersection = the sum in face order, IoU = inter / (vol a + vol b - inter).
+ *   Tie rule: a vertex ON a clipping plane is inside only while a's faces are clipped by b and only if the face's outward normal
+ *   and the plane's normal have a positive dot product; otherwise outside.  (Identical boxes then count every shared face once,
+ *   touching boxes never.)  ON = a signed distance within 2^-26 x the largest half extent of the two boxes, which is then taken
+ *   as 0: an exact test would leave coincident faces of turned boxes to the sign of a rounding error (a box against itself
+ *   anywhere between 0.1 and 15).  Accuracy: round-off for boxes in general position; where two faces meet at a small angle a the
+ *   intersection points are conditioned like eps / a, so the worst case is about sqrt(eps) ~ 1e-8 near a = 2^-26 rad.
+ *   A pair with a non-finite corner or a zero extent gives NaN.
+ * gpn_pose_pair_errors for P pairs: (scale [P], rotation [P,3,3], translation [P,3], half [P,3]) of prediction and ground truth,
+ *   sym_type [P] i32, and the candidate table sym_table [K,3,3] f64 with sym_start, sym_count [T] i32 per type (count <= 24), all on
+ *   the device.  With F_k = S_k R_gt for the type's candidates k in table order:
+ *     re_deg = min_k atan2(|v|, (tr M - 1) / 2) in degrees, M = R_pred F_k^T, v = vee of (M - M^T) / 2; k_re = the first minimiser;
+ *     te = |t_pred - t_gt|; se = |s_pred - s_gt|;
+ *     iou = max_k IoU(box(s_pred, R_pred, t_pred, half_pred), box(s_gt, F_k, t_gt, half_gt)) by the rule above; k_iou = the first
+ *     maximiser.  (k counts inside the type: 0 is the type's first candidate.)
+ *   Non-finite poses give NaN (and k = 0); a type outside 0 .. T-1 or a table range outside 0 .. K gives NaN and k = -1.
+ * ================================================================================================ */
+int gpn_pose_gt_fit(const float* xyz, const float* npcs, const int32_t* slot, const int64_t* scene_offsets, int64_t N, int S, int W,
+                    int64_t* count, uint8_t* valid, double* scale, double* rotation, double* translation, double* half, double* bbox,
+                    gpn_stream_t stream);
+int gpn_box_iou_3d(const double* a, const double* b, int64_t P, double* iou, gpn_stream_t stream);
+int gpn_pose_pair_errors(const double* scale_pred, const double* rotation_pred, const double* translation_pred, const double* half_pred,
+                         const double* scale_gt, const double* rotation_gt, const double* translation_gt, const double* half_gt,
+                         const int32_t* sym_type, int64_t P, const double* sym_table, int K, const int32_t* sym_start,
+                         const int32_t* sym_count, int T, double* re_deg, int32_t* k_re, double* te, double* se, double* iou,
+                         int32_t* k_iou, gpn_stream_t stream);
+
+/* ================================================================================================
  * VS - test-time part predictions and the 3 x 4 panel of images per sampled scene (the reference's on_test_epoch_end,
  * network/model.py:930-999, misc/visu.py, misc/visu_util.py).  Every "the last writer of the loop wins" of the reference is an
  * integer atomicMax over the writer's position and a resolve pass: results are bit-reproducible and never depend on timing; no
