@@ -52,6 +52,7 @@ const char* kEntryPoints[] = {
     "gpn_joint_sample", "gpn_cpd_rigid", "gpn_joint_from_rigid",
     "gpn_pose_gt_fit", "gpn_box_iou_3d", "gpn_pose_pair_errors",
     "gpn_render_max_links", "gpn_render_ws_bytes", "gpn_render_setup", "gpn_render_raster", "gpn_render_annotate",
+    "gpn_render_max_lights", "gpn_render_shade",
     "gpn_last_error", "gpn_version"};
 }  // namespace
 

@@ -4,6 +4,9 @@
 //   raster    one 256-lane workgroup per 16 x 16 tile per view, one pixel per lane: box scan in chunks of 256, ballot compaction
 //             into LDS, int64 edge functions with the top-left rule, float64 1/z interpolation; every pixel stored once
 //   annotate  link areas (LDS histogram, integer atomics), instance ids in annotation order, per-pixel sem / ins / NPCS / RGB
+//   shade     section RS, opt-in: one 256-lane workgroup per 16 x 16 tile per view, one pixel per lane; the winner's corners are
+//             projected again by the function setup uses, perspective-correct uv, bilinear wrapping texel fetch, the view's light
+//             rows from LDS; overwrites the RGB of annotate, every byte once, no atomics, no workspace
 // No float atomics and no binning workspace: the images do not depend on launch order.  -ffp-contract=off: every float64
 // expression below is evaluated exactly as written.
 #include <cmath>
@@ -60,6 +63,38 @@ __device__ __forceinline__ AssetSpan asset_span(const int32_t* __restrict__ asse
   return s;
 }
 
+// camera-space corners P (parsed vertex order) and their screen positions snapped to 1/256 px, shared by setup and shade so that
+// both see the same bits.  -> -1, or the drop rule that applies first (GPN_RENDER_DROP_INDEX / _NEAR / _GUARD)
+__device__ __forceinline__ int project_triangle(const float* __restrict__ verts, int Nv, const int32_t* __restrict__ tris,
+                                                const int32_t* __restrict__ tri_visual, int t, int visuals, int M,
+                                                const double* __restrict__ c, const double* __restrict__ view_mat,
+                                                double (&P)[3][3], int (&X)[3], int (&Y)[3]) {
+  const int vis = tri_visual[t];
+  const int i0 = tris[t * 3], i1 = tris[t * 3 + 1], i2 = tris[t * 3 + 2];
+  if (vis < 0 || vis >= M || vis >= visuals || i0 < 0 || i0 >= Nv || i1 < 0 || i1 >= Nv || i2 < 0 || i2 >= Nv)
+    return GPN_RENDER_DROP_INDEX;
+  const double fx = c[0], fy = c[1], cx = c[2], cy = c[3];
+  const double* m = view_mat + (int64_t)vis * 12;
+  const int idx[3] = {i0, i1, i2};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double x = (double)verts[idx[j] * 3], y = (double)verts[idx[j] * 3 + 1], z = (double)verts[idx[j] * 3 + 2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) P[j][r] = ((m[r * 4] * x + m[r * 4 + 1] * y) + m[r * 4 + 2] * z) + m[r * 4 + 3];
+  }
+  if (!(P[0][2] >= kNear && P[1][2] >= kNear && P[2][2] >= kNear)) return GPN_RENDER_DROP_NEAR;  // (a NaN depth is dropped here too)
+  bool guard = false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double u = (fx * P[j][0]) / P[j][2] + cx, w = (fy * P[j][1]) / P[j][2] + cy;
+    const double su = rint(u * 256.0), sv = rint(w * 256.0);
+    guard |= !(fabs(su) <= (double)kGuard && fabs(sv) <= (double)kGuard);
+    X[j] = (int)su;
+    Y[j] = (int)sv;
+  }
+  return guard ? GPN_RENDER_DROP_GUARD : -1;
+}
+
 // ---- setup -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rd_setup_kernel(const float* __restrict__ verts, int Nv, const int32_t* __restrict__ tris,
                                                        const int32_t* __restrict__ tri_visual, int Nt,
@@ -79,47 +114,18 @@ __global__ __launch_bounds__(256) void rd_setup_kernel(const float* __restrict__
     return;
   }
   const int t = sp.first + k;
-  const int vis = tri_visual[t];
-  const int i0 = tris[t * 3], i1 = tris[t * 3 + 1], i2 = tris[t * 3 + 2];
   int32_t* cnt = counters + v * GPN_RENDER_COUNTERS;
-  if (vis < 0 || vis >= M || vis >= sp.visuals || i0 < 0 || i0 >= Nv || i1 < 0 || i1 >= Nv || i2 < 0 || i2 >= Nv) {
-    atomicAdd(cnt + GPN_RENDER_DROP_INDEX, 1);
-    *bo = none;
-    return;
-  }
   const double* c = cam + (int64_t)v * kCam;
-  const double fx = c[0], fy = c[1], cx = c[2], cy = c[3];
-  const double* m = vis_mat + ((int64_t)v * M + vis) * 12;
-  const int idx[3] = {i0, i1, i2};
   double P[3][3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const double x = (double)verts[idx[j] * 3], y = (double)verts[idx[j] * 3 + 1], z = (double)verts[idx[j] * 3 + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) P[j][r] = ((m[r * 4] * x + m[r * 4 + 1] * y) + m[r * 4 + 2] * z) + m[r * 4 + 3];
-  }
-  if (!(P[0][2] >= kNear && P[1][2] >= kNear && P[2][2] >= kNear)) {  // (a NaN depth is dropped here too)
-    atomicAdd(cnt + GPN_RENDER_DROP_NEAR, 1);
-    *bo = none;
-    return;
-  }
-  double su[3], sv[3];
-  bool guard = false;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const double u = (fx * P[j][0]) / P[j][2] + cx, w = (fy * P[j][1]) / P[j][2] + cy;
-    su[j] = rint(u * 256.0);
-    sv[j] = rint(w * 256.0);
-    guard |= !(fabs(su[j]) <= (double)kGuard && fabs(sv[j]) <= (double)kGuard);
-  }
-  if (guard) {
-    atomicAdd(cnt + GPN_RENDER_DROP_GUARD, 1);
+  int X[3], Y[3];
+  const int drop = project_triangle(verts, Nv, tris, tri_visual, t, sp.visuals, M, c, vis_mat + (int64_t)v * M * 12, P, X, Y);
+  if (drop >= 0) {
+    atomicAdd(cnt + drop, 1);
     *bo = none;
     return;
   }
   TriRec r;
   int o[3] = {0, 1, 2};
-  int X[3] = {(int)su[0], (int)su[1], (int)su[2]}, Y[3] = {(int)sv[0], (int)sv[1], (int)sv[2]};
   const int64_t area2 = edge_fn(X[0], Y[0], X[1], Y[1], X[2], Y[2]);
   if (area2 == 0) {
     atomicAdd(cnt + GPN_RENDER_DROP_ZERO_AREA, 1);
@@ -335,6 +341,139 @@ __global__ __launch_bounds__(256) void rd_pixel_kernel(const float* __restrict__
   rgb[o * 3] = (uint8_t)col[0]; rgb[o * 3 + 1] = (uint8_t)col[1]; rgb[o * 3 + 2] = (uint8_t)col[2];
 }
 
+// ---- shade (section RS) ------------------------------------------------------------------------------------------------------
+constexpr int kMaxLights = 16;
+constexpr int kLight = 8;  // doubles per light: kind | x y z | r g b | pad
+
+__device__ __forceinline__ int wrap_index(int i, int n) {  // i mod n for i in [-1, n]
+  return i < 0 ? i + n : (i >= n ? i - n : i);
+}
+
+__global__ __launch_bounds__(kLanes) void rs_shade_kernel(
+    const float* __restrict__ verts, int Nv, const int32_t* __restrict__ tris, const int32_t* __restrict__ tri_visual,
+    const float* __restrict__ tri_color, int Nt, const int32_t* __restrict__ assets, int A, const int32_t* __restrict__ view_asset,
+    const double* __restrict__ cam, const double* __restrict__ vis_mat, int M, const float* __restrict__ tri_uv,
+    const int32_t* __restrict__ tri_tex, const int32_t* __restrict__ tex_table, int T, const uint32_t* __restrict__ tex_data,
+    int64_t texels, const double* __restrict__ lights, int NL, const float* __restrict__ depth, const int32_t* __restrict__ tri,
+    int H, int W, int Nt_max, int bg_r, int bg_g, int bg_b, uint8_t* __restrict__ rgb) {
+  __shared__ double s_light[kMaxLights * kLight];
+  const int v = blockIdx.z;
+  const int tid = threadIdx.x;
+  if (tid < NL * kLight) s_light[tid] = lights[(int64_t)v * NL * kLight + tid];  // NL <= 16: at most 128 lanes load
+  __syncthreads();
+  const int px = blockIdx.x * kTile + (tid & (kTile - 1)), py = blockIdx.y * kTile + (tid >> 4);
+  if (px >= W || py >= H) return;
+  const int64_t o = ((int64_t)v * H + py) * W + px;
+  const AssetSpan sp = asset_span(assets, A, view_asset, v, Nt);
+  const int t = tri[o];
+  int col[3] = {bg_r, bg_g, bg_b};
+  double P[3][3];
+  int X[3], Y[3];
+  const double* c = cam + (int64_t)v * kCam;
+  bool drawn = t >= sp.first && t < sp.first + min(sp.count, Nt_max);
+  if (drawn) drawn = project_triangle(verts, Nv, tris, tri_visual, t, sp.visuals, M, c, vis_mat + (int64_t)v * M * 12, P, X, Y) < 0;
+  int64_t area2 = 0;
+  if (drawn) {
+    area2 = edge_fn(X[0], Y[0], X[1], Y[1], X[2], Y[2]);
+    drawn = area2 != 0;  // (the raster never hands out such a triangle)
+  }
+  if (drawn) {
+    // barycentrics over the oriented corners (0, 1, 2) or (0, 2, 1), perspective-corrected, back in parsed order
+    const bool flip = area2 < 0;
+    const int x1 = flip ? X[2] : X[1], y1 = flip ? Y[2] : Y[1], x2 = flip ? X[1] : X[2], y2 = flip ? Y[1] : Y[2];
+    const double z1 = flip ? P[2][2] : P[1][2], z2 = flip ? P[1][2] : P[2][2];
+    const int sx = px * 256, sy = py * 256;
+    const int64_t e0 = edge_fn(x1, y1, x2, y2, sx, sy), e1 = edge_fn(x2, y2, X[0], Y[0], sx, sy), e2 = edge_fn(X[0], Y[0], x1, y1, sx, sy);
+    const double a2 = (double)((e0 + e1) + e2);
+    const double w0 = ((double)e0 / a2) * (1.0 / P[0][2]), w1 = ((double)e1 / a2) * (1.0 / z1), w2 = ((double)e2 / a2) * (1.0 / z2);
+    const double ws = (w0 + w1) + w2;
+    const double b0 = w0 / ws, bo1 = w1 / ws, bo2 = w2 / ws;
+    const double b1 = flip ? bo2 : bo1, b2 = flip ? bo1 : bo2;
+    // albedo in 0 ... 255
+    double alb[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) alb[r] = (double)tri_color[(int64_t)t * 3 + r] * 255.0;
+    int tx = T > 0 ? tri_tex[t] : -1;
+    int tw = 0, th = 0;
+    int64_t first = 0;
+    if (tx >= 0 && tx < T) {
+      first = tex_table[tx * 4];
+      tw = tex_table[tx * 4 + 1];
+      th = tex_table[tx * 4 + 2];
+      if (first < 0 || tw < 1 || th < 1 || (int64_t)tw * th > texels - first) tx = -1;  // (refused on the host as well)
+    } else {
+      tx = -1;
+    }
+    if (tx >= 0) {
+      const float* q = tri_uv + (int64_t)t * 6;
+      const float u0 = q[0], v0 = q[1], u1 = q[2], v1 = q[3], u2 = q[4], v2 = q[5];
+      if (isfinite(u0) && isfinite(v0) && isfinite(u1) && isfinite(v1) && isfinite(u2) && isfinite(v2)) {
+        const double tu = (b0 * (double)u0 + b1 * (double)u1) + b2 * (double)u2;
+        const double tv = (b0 * (double)v0 + b1 * (double)v1) + b2 * (double)v2;
+        const double fv = 1.0 - tv;
+        const double uu = tu - floor(tu), vv = fv - floor(fv);
+        if (uu >= 0.0 && uu <= 1.0 && vv >= 0.0 && vv <= 1.0) {  // (false only for a NaN: b is finite for a drawn pixel)
+          const double Xc = uu * (double)tw - 0.5, Yc = vv * (double)th - 0.5;
+          const double fi = floor(Xc), fk = floor(Yc);
+          const double fx = Xc - fi, fy = Yc - fk;
+          const int i0 = wrap_index((int)fi, tw), i1 = wrap_index((int)fi + 1, tw);
+          const int k0 = wrap_index((int)fk, th), k1 = wrap_index((int)fk + 1, th);
+          const uint32_t a00 = tex_data[first + (int64_t)k0 * tw + i0], a01 = tex_data[first + (int64_t)k0 * tw + i1];
+          const uint32_t a10 = tex_data[first + (int64_t)k1 * tw + i0], a11 = tex_data[first + (int64_t)k1 * tw + i1];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            const double c00 = (double)((a00 >> (8 * r)) & 255u), c01 = (double)((a01 >> (8 * r)) & 255u);
+            const double c10 = (double)((a10 >> (8 * r)) & 255u), c11 = (double)((a11 >> (8 * r)) & 255u);
+            alb[r] = (c00 * (1.0 - fx) + c01 * fx) * (1.0 - fy) + (c10 * (1.0 - fx) + c11 * fx) * fy;
+          }
+        }
+      }
+    }
+    // flat two-sided normal, towards the camera
+    const double ax = P[1][0] - P[0][0], ay = P[1][1] - P[0][1], az = P[1][2] - P[0][2];
+    const double bx = P[2][0] - P[0][0], by = P[2][1] - P[0][1], bz = P[2][2] - P[0][2];
+    double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const double nn = sqrt((nx * nx + ny * ny) + nz * nz);
+    const bool lit = nn > 0.0;
+    if (lit) {
+      nx = nx / nn; ny = ny / nn; nz = nz / nn;
+      if ((nx * P[0][0] + ny * P[0][1]) + nz * P[0][2] > 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+    }
+    const double z = (double)depth[o];
+    const double p0 = (((double)px - c[2]) * z) / c[0], p1 = (((double)py - c[3]) * z) / c[1];
+    double I[3] = {0.0, 0.0, 0.0};
+    for (int l = 0; l < NL; ++l) {
+      const double* s = s_light + l * kLight;
+      const double kind = s[0];
+      if (kind == 0.0) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) I[r] = I[r] + s[4 + r];
+      } else if (kind == 1.0 && lit) {
+        const double nd = (nx * s[1] + ny * s[2]) + nz * s[3];
+        const double m = nd > 0.0 ? nd : 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) I[r] = I[r] + s[4 + r] * m;
+      } else if (kind == 2.0 && lit) {
+        const double dx = s[1] - p0, dy = s[2] - p1, dz = s[3] - z;
+        const double r2 = (dx * dx + dy * dy) + dz * dz;
+        const double rr = sqrt(r2);
+        if (rr > 0.0) {
+          const double nd = ((nx * dx + ny * dy) + nz * dz) / rr;
+          const double m = nd > 0.0 ? nd : 0.0;
+#pragma unroll
+          for (int r = 0; r < 3; ++r) I[r] = I[r] + (s[4 + r] * m) / r2;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double val = rint(alb[r] * I[r]);
+      col[r] = val >= 255.0 ? 255 : (val > 0.0 ? (int)val : 0);
+    }
+  }
+  rgb[o * 3] = (uint8_t)col[0]; rgb[o * 3 + 1] = (uint8_t)col[1]; rgb[o * 3 + 2] = (uint8_t)col[2];
+}
+
 int check_shape(const char* who, int V, int H, int W, int Nt_max) {
   if (!(V >= 0 && V <= 65535 && H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && Nt_max >= 0 &&
         (int64_t)V * H * W < (int64_t)0x7fffffff && (int64_t)V * (Nt_max > 0 ? Nt_max : 1) < (int64_t)0x7fffffff)) {
@@ -430,6 +569,32 @@ extern "C" int gpn_render_annotate(const float* depth, const int32_t* tri, const
   hipLaunchKernelGGL(rd_pixel_kernel, dim3((unsigned)gpn::cdiv(HW, 256), (unsigned)V), dim3(256), 0, stream, depth, tri, tri_link,
                      tri_color, Nt, assets, A, view_asset, cam, link_cat, link_inst, link_frame, L, H, W, Nt_max, rw.recs, bg_r,
                      bg_g, bg_b, sem, ins, npcs, rgb);
+  GPN_CHECK_LAUNCH();
+  return GPN_OK;
+}
+
+extern "C" int gpn_render_max_lights(void) { return kMaxLights; }
+
+extern "C" int gpn_render_shade(const float* verts, int Nv, const int32_t* tris, const int32_t* tri_visual, const float* tri_color,
+                                int Nt, const int32_t* assets, int A, const int32_t* view_asset, const double* cam,
+                                const double* vis_mat, int M, const float* tri_uv, const int32_t* tri_tex, const int32_t* tex_table,
+                                int T, const void* tex_data, int64_t texels, const double* lights, int NL, const float* depth,
+                                const int32_t* tri, int V, int H, int W, int Nt_max, int bg_r, int bg_g, int bg_b, uint8_t* rgb,
+                                gpn_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (int rc = check_shape(__func__, V, H, W, Nt_max)) return rc;
+  GPN_CHECK_ARG(Nv >= 0 && Nt >= 0 && A >= 0 && M >= 0 && Nt_max <= Nt && (int64_t)Nv * 3 < (int64_t)0x7fffffff &&
+                (int64_t)Nt * 6 < (int64_t)0x7fffffff);
+  GPN_CHECK_ARG(NL >= 0 && NL <= kMaxLights);
+  GPN_CHECK_ARG(T >= 0 && T <= 0x7fffffff / 4 && texels >= 0 && texels < (int64_t)0x7fffffff);
+  GPN_CHECK_ARG(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255);
+  if (V == 0) return GPN_OK;
+  GPN_CHECK_ARG(depth && tri && rgb && view_asset && cam && (A == 0 || assets) && (NL == 0 || lights));
+  GPN_CHECK_ARG(Nt_max == 0 || (verts && tris && tri_visual && tri_color && assets && vis_mat && M >= 1));
+  GPN_CHECK_ARG(T == 0 || (tri_uv && tri_tex && tex_table && tex_data && texels >= T));
+  hipLaunchKernelGGL(rs_shade_kernel, dim3((unsigned)gpn::cdiv(W, kTile), (unsigned)gpn::cdiv(H, kTile), (unsigned)V), dim3(kLanes),
+                     0, stream, verts, Nv, tris, tri_visual, tri_color, Nt, assets, A, view_asset, cam, vis_mat, M, tri_uv, tri_tex,
+                     tex_table, T, (const uint32_t*)tex_data, texels, lights, NL, depth, tri, H, W, Nt_max, bg_r, bg_g, bg_b, rgb);
   GPN_CHECK_LAUNCH();
   return GPN_OK;
 }

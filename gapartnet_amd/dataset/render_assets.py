@@ -13,8 +13,10 @@ of views is rasterised by the kernels of include/gpn.h section RD: one kernel ba
     write_view(out, "StorageFurniture_45780_0_0", view)
 
 On a CPU device ``render_views`` runs ``render_tables_numpy``, a vectorised numpy formulation of the same contracts (the baseline of
-tools/render_bench.py, and what a machine without a GPU can check).  RGB is flat-shaded base colour: textures, point lights,
-shadows, ray tracing and ``replace_texture`` are out of scope; depth, labels, NPCS, boxes and metadata are the contract.
+tools/render_bench.py, and what a machine without a GPU can check).  Depth, labels, NPCS, boxes and metadata are the contract.
+RGB is flat-shaded base colour by default; ``shading="textured"`` (with ``load_asset(..., textures=True)``) samples the map_Kd
+textures bilinearly and lights them with a table of ambient, directional and point lights (``REFERENCE_LIGHTS``: the reference's
+rig; include/gpn.h section RS).  Shadows, specular terms, smooth normals, ray tracing and ``replace_texture`` are out of scope.
 
 DECISIONS: the camera frame of ``camera_frame``; polygons are fan-triangulated; triangles with a vertex nearer
 than 0.1 are dropped whole; pixel (x, y) samples the ray through u = x, v = y.
@@ -24,6 +26,7 @@ import json
 import math
 import os
 import pickle
+import re
 import sys
 import time
 import xml.etree.ElementTree as ET
@@ -46,6 +49,16 @@ FOV_DEG = 35.0
 DEFAULT_CAMERA_RANGE = dict(theta_min=35.0, theta_max=75.0, phi_min=135.0, phi_max=225.0, distance_min=3.6, distance_max=4.4)
 COUNTER_NAMES = ("index", "near", "guard", "zero_area", "offscreen")
 CAM_DOUBLES, FRAME_DOUBLES = 20, 13
+SHADINGS = ("flat", "textured")
+LIGHT_AMBIENT, LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1, 2
+MAX_LIGHTS, LIGHT_DOUBLES = 16, 8
+# the reference's light rig (render_utils.py:73-77) in world coordinates, rows of (kind, x y z, r g b): for a directional light x y z
+# is the direction the light TRAVELS along (as the reference gives it), for a point light its position
+REFERENCE_LIGHTS = ((LIGHT_AMBIENT, (0.0, 0.0, 0.0), (0.5, 0.5, 0.5)),
+                    (LIGHT_DIRECTIONAL, LIGHT_WORLD, (0.5, 0.5, 0.5)),
+                    (LIGHT_POINT, (1.0, 2.0, 2.0), (1.0, 1.0, 1.0)),
+                    (LIGHT_POINT, (1.0, -2.0, 2.0), (1.0, 1.0, 1.0)),
+                    (LIGHT_POINT, (-1.0, 0.0, 1.0), (1.0, 1.0, 1.0)))
 NEAR, GUARD = 0.1, 16384 * 256
 
 
@@ -122,6 +135,131 @@ def read_mtl(path):
     return out
 
 
+_MAP_OPTION_ARGS = {'o': 3, 's': 3, 't': 3, 'mm': 2}  # numbers an option takes at the most (the others take one word)
+
+
+def _map_file(rest):
+    """the file name of a map_Kd statement: options in front of it are skipped, the rest of the line is the name (spaces kept)"""
+    rest = rest.strip()
+    while True:
+        m = re.match(r'-(\w+)\s+', rest)
+        if not m:
+            break
+        rest = rest[m.end():]
+        numeric = m.group(1) in _MAP_OPTION_ARGS
+        for _ in range(_MAP_OPTION_ARGS.get(m.group(1), 1)):
+            a = re.match(r'(\S+)\s+', rest)  # (never the last word of the line: that is the file)
+            if not a:
+                break
+            if numeric:
+                try:
+                    float(a.group(1))
+                except ValueError:
+                    break
+            rest = rest[a.end():]
+    return rest.replace('\\', '/')
+
+
+def read_mtl_textured(path):
+    """material name -> {'Kd': [r, g, b] (0.8 grey when the material has none), 'map_Kd': path of the texture file or None}.
+    Options in front of the file name are skipped, backslashes read as '/', the path is relative to the MTL file's directory."""
+    out, cur = {}, None
+    if not os.path.exists(path):
+        return out
+    base = os.path.dirname(path)
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == 'newmtl':
+                cur = ' '.join(tok[1:])
+                out[cur] = dict(Kd=[DEFAULT_GREY] * 3, map_Kd=None)
+            elif tok[0] == 'Kd' and cur is not None and len(tok) >= 4:
+                out[cur]['Kd'] = [float(tok[1]), float(tok[2]), float(tok[3])]
+            elif tok[0] == 'map_Kd' and cur is not None and len(tok) >= 2:
+                name = _map_file(line.split(None, 1)[1])
+                if name:
+                    out[cur]['map_Kd'] = os.path.normpath(os.path.join(base, name))
+    return out
+
+
+def read_obj_textured(path):
+    """read_obj plus texture coordinates -> (verts, tris, colours, tri_uv [m,3,2] f32, tri_material [m] i32, materials).  tri_uv is
+    the `vt` of each corner in parsed corner order, NaN where a corner has none (forms a, a/b, a//c, a/b/c; negative vt indices
+    count back from the last vt read; the fan keeps each corner's vt).  tri_material is a row of `materials`, the list of
+    {'name', 'Kd', 'map_Kd', 'mtl'} in the order usemtl first names them, -1 under no (or an unknown) material."""
+    verts, vts, tris, cols, uvs, tmat = [], [], [], [], [], []
+    mats, kd, cur = {}, [DEFAULT_GREY] * 3, -1
+    used, materials = {}, []
+    base = os.path.dirname(path)
+    nan = float('nan')
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == 'v':
+                verts.append([float(tok[1]), float(tok[2]), float(tok[3])])
+            elif tok[0] == 'vt':
+                vts.append([float(tok[1]), float(tok[2]) if len(tok) > 2 else 0.0])
+            elif tok[0] == 'mtllib':
+                for name in tok[1:]:
+                    lib = os.path.normpath(os.path.join(base, name))
+                    mats.update({k: dict(m, mtl=lib) for k, m in read_mtl_textured(lib).items()})
+            elif tok[0] == 'usemtl':
+                name = ' '.join(tok[1:])
+                if name in mats:
+                    if name not in used:
+                        used[name] = len(materials)
+                        materials.append(dict(name=name, **mats[name]))
+                    cur, kd = used[name], mats[name]['Kd']
+                else:
+                    cur, kd = -1, [DEFAULT_GREY] * 3
+            elif tok[0] == 'f':
+                idx, tex = [], []
+                for t in tok[1:]:
+                    part = t.split('/')
+                    i = int(part[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if not 0 <= i < len(verts):
+                        raise ValueError(f'{path}: face index {t} outside the {len(verts)} vertices read so far')
+                    idx.append(i)
+                    if len(part) > 1 and part[1]:
+                        j = int(part[1])
+                        j = j - 1 if j > 0 else len(vts) + j
+                        if not 0 <= j < len(vts):
+                            raise ValueError(f'{path}: face index {t} outside the {len(vts)} texture coordinates read so far')
+                        tex.append(vts[j])
+                    else:
+                        tex.append([nan, nan])
+                for j in range(1, len(idx) - 1):
+                    tris.append([idx[0], idx[j], idx[j + 1]])
+                    uvs.append([tex[0], tex[j], tex[j + 1]])
+                    cols.append(kd)
+                    tmat.append(cur)
+    return (np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(tris, np.int32).reshape(-1, 3),
+            np.asarray(cols, np.float32).reshape(-1, 3), np.asarray(uvs, np.float32).reshape(-1, 3, 2),
+            np.asarray(tmat, np.int32).reshape(-1), materials)
+
+
+def load_texture(path, max_texture_size=None):
+    """an image file -> [h,w,3] u8 (PIL, imported here), box-downscaled by a whole factor until no side exceeds max_texture_size;
+    None when the file cannot be opened or decoded"""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("load_asset(textures=True) decodes map_Kd images with PIL (Pillow), which is not installed") from e
+    try:
+        with Image.open(path) as img:
+            img = img.convert('RGB')
+            if max_texture_size and max(img.size) > int(max_texture_size):
+                img = img.reduce(-(-max(img.size) // int(max_texture_size)))
+            return np.ascontiguousarray(np.asarray(img, np.uint8))
+    except (OSError, ValueError):
+        return None
+
+
 def read_obj(path):
     """-> (verts [n,3] f32, tris [m,3] i32, colours [m,3] f32).  `v` and `f` lines only; a/b/c forms and negative (relative)
     indices; polygons are fan-triangulated around their first vertex (DECISION); the colour of a face is the Kd of the active
@@ -172,6 +310,12 @@ class Asset:
     targets: Dict[str, dict]           # annotation order: link name -> {category_id, bbox [8,3] f32}
     link_cat: np.ndarray = field(default=None)   # [L] i32, -1 for a link that is no target
     link_rank: np.ndarray = field(default=None)  # [L] i32, position in the annotation file, -1 likewise
+    # load_asset(textures=True) only:
+    tri_uv: np.ndarray = field(default=None)     # [Nt,3,2] f32, NaN where a corner has no vt
+    tri_tex: np.ndarray = field(default=None)    # [Nt] i32, row of textures, -1 where the triangle is shaded with its Kd
+    textures: List[np.ndarray] = field(default=None)  # [h,w,3] u8 each, one per distinct map_Kd file that could be opened
+    missing_textures: int = 0                    # MTL files with a material in use whose map_Kd file could not be opened ...
+    missing_texture_files: int = 0               # ... and the distinct image files they name
 
 
 def read_targets(anno_path):
@@ -183,12 +327,16 @@ def read_targets(anno_path):
             for e in entries if e['is_gapart'] and e['category'] in known}
 
 
-def load_asset(path, urdf="mobility_annotation_gapartnet.urdf", anno="link_annotation_gapartnet.json", base_link_name="base"):
+def load_asset(path, urdf="mobility_annotation_gapartnet.urdf", anno="link_annotation_gapartnet.json", base_link_name="base",
+               textures=False, max_texture_size=None):
+    """textures=True: the asset also carries tri_uv, tri_tex, textures and missing_textures (decoding needs PIL).  A triangle keeps
+    its Kd (tri_tex -1) when its material has no map_Kd, the file cannot be opened or a corner has no vt."""
     urdf_path = os.path.join(path, urdf)
     root = ET.parse(urdf_path).getroot()
     joints = read_joints(urdf_path)
     links, v_link, v_origin = [], [], []
     verts, tris, tri_visual, tri_link, tri_color = [], [], [], [], []
+    tri_uv, tri_tex, images, slot, missing = [], [], [], {}, set()  # slot: texture file -> row of images, -1 for a file that failed
     nv = 0
     for li, link in enumerate(root.findall('link')):
         links.append(link.attrib['name'])
@@ -199,7 +347,25 @@ def load_asset(path, urdf="mobility_annotation_gapartnet.urdf", anno="link_annot
             mesh = visual.find('geometry').find('mesh')
             if mesh is None:
                 continue
-            v, t, c = read_obj(os.path.join(path, mesh.attrib['filename']))
+            if textures:
+                v, t, c, uv, tm, materials = read_obj_textured(os.path.join(path, mesh.attrib['filename']))
+                rows = []
+                for m in materials:
+                    f = m['map_Kd']
+                    if f is not None and f not in slot:
+                        img = load_texture(f, max_texture_size)
+                        slot[f] = len(images) if img is not None else -1
+                        if img is not None:
+                            images.append(img)
+                    rows.append(slot[f] if f is not None else -1)
+                    if f is not None and slot[f] < 0:
+                        missing.add(m['mtl'])
+                tx = np.where(tm >= 0, np.asarray(rows + [-1], np.int32)[tm], -1).astype(np.int32)
+                tx[np.isnan(uv).any(axis=(1, 2))] = -1
+                tri_uv.append(uv)
+                tri_tex.append(tx)
+            else:
+                v, t, c = read_obj(os.path.join(path, mesh.attrib['filename']))
             scale = _floats(mesh.attrib.get('scale'), (1, 1, 1))
             o = _pose(xyz, rpy)
             o[:3, :3] = o[:3, :3] * np.asarray(scale, np.float64)[None, :]
@@ -221,6 +387,10 @@ def load_asset(path, urdf="mobility_annotation_gapartnet.urdf", anno="link_annot
                   visual_link=np.asarray(v_link, np.int32), visual_origin=np.asarray(v_origin, np.float64).reshape(-1, 4, 4),
                   verts=cat(verts, (0, 3), np.float32), tris=cat(tris, (0, 3), np.int32), tri_visual=cat(tri_visual, (0,), np.int32),
                   tri_link=cat(tri_link, (0,), np.int32), tri_color=cat(tri_color, (0, 3), np.float32), targets=targets)
+    if textures:
+        asset.tri_uv, asset.tri_tex = cat(tri_uv, (0, 3, 2), np.float32), cat(tri_tex, (0,), np.int32)
+        asset.textures, asset.missing_textures = images, len(missing)
+        asset.missing_texture_files = sum(1 for i in slot.values() if i < 0)
     asset.link_cat = np.full(len(links), -1, np.int32)
     asset.link_rank = np.full(len(links), -1, np.int32)
     for rank, (name, d) in enumerate(targets.items()):
@@ -431,23 +601,80 @@ def geometry_tables(assets):
         v0 += len(a.verts)
         t0 += len(a.tris)
     z = np.zeros
-    return dict(verts=np.concatenate(verts).astype(np.float32) if assets else z((0, 3), np.float32),
+    g = dict(verts=np.concatenate(verts).astype(np.float32) if assets else z((0, 3), np.float32),
                 tris=np.concatenate(tris).astype(np.int32) if assets else z((0, 3), np.int32),
                 tri_visual=np.concatenate([a.tri_visual for a in assets]).astype(np.int32) if assets else z((0,), np.int32),
                 tri_link=np.concatenate([a.tri_link for a in assets]).astype(np.int32) if assets else z((0,), np.int32),
                 tri_color=np.concatenate([a.tri_color for a in assets]).astype(np.float32) if assets else z((0, 3), np.float32),
-                assets=np.asarray(table, np.int32).reshape(-1, 4))
+             assets=np.asarray(table, np.int32).reshape(-1, 4))
+    if any(a.textures for a in assets):  # section RS: only when some asset has a texture
+        uv, tex, rows, texels, n_tex = [], [], [], 0, 0
+        for a in assets:
+            has = bool(a.textures)
+            uv.append(a.tri_uv if has else np.full((len(a.tris), 3, 2), np.nan, np.float32))
+            tex.append(np.where(a.tri_tex >= 0, a.tri_tex + n_tex, -1) if has else np.full(len(a.tris), -1, np.int32))
+            for img in (a.textures or []):
+                rows.append([texels, img.shape[1], img.shape[0], 0])
+                texels += img.shape[0] * img.shape[1]
+            n_tex += len(a.textures or [])
+        if texels >= 2 ** 31:
+            raise ValueError(f"the batch's textures hold {texels} texels, the tables address fewer than 2^31: load the assets "
+                             f"with max_texture_size or put fewer assets into a batch")
+        data = np.full((texels, 4), 255, np.uint8)
+        o = 0
+        for a in assets:
+            for img in (a.textures or []):
+                data[o:o + img.shape[0] * img.shape[1], :3] = img.reshape(-1, 3)
+                o += img.shape[0] * img.shape[1]
+        g.update(tri_uv=np.concatenate(uv).astype(np.float32), tri_tex=np.concatenate(tex).astype(np.int32),
+                 tex_table=np.asarray(rows, np.int32).reshape(-1, 4), tex_data=data)
+    return g
 
 
-def view_tables(assets, requests, H, W):
-    """the per-view tables of section RD, plus what the files need -> (tables, per-view extras)"""
+def check_texture_tables(g):
+    """the contents of the section-RS geometry tables, checked on the host before any upload (the kernel bounds-checks them too)"""
+    if g.get('tex_table') is None or not len(g['tex_table']):
+        return
+    T, texels = len(g['tex_table']), len(g['tex_data'])
+    tt = g['tex_table'].astype(np.int64)
+    if len(g['tri_tex']) != len(g['tris']) or len(g['tri_uv']) != len(g['tris']):
+        raise ValueError("tri_uv and tri_tex need one row per triangle")
+    if ((g['tri_tex'] < -1) | (g['tri_tex'] >= T)).any():
+        raise ValueError(f"tri_tex outside [-1, {T})")
+    if ((tt[:, 0] < 0) | (tt[:, 1] < 1) | (tt[:, 2] < 1) | (tt[:, 0] + tt[:, 1] * tt[:, 2] > texels)).any():
+        raise ValueError(f"a tex_table row spans texels outside tex_data ({texels} texels)")
+
+
+def light_rows(lights, R, tr):
+    """world-space lights (rows of (kind, xyz, rgb) like REFERENCE_LIGHTS) -> [NL,8] f64 in the camera frame (camera point = (world
+    - tr) @ R): kind | x y z | r g b | pad, a directional row holding the unit vector TOWARDS the light"""
+    rows = np.zeros((len(lights), LIGHT_DOUBLES))
+    for i, (kind, xyz, rgb) in enumerate(lights):
+        xyz = np.asarray(xyz, np.float64)
+        if kind == LIGHT_DIRECTIONAL:
+            xyz = (-xyz / np.linalg.norm(xyz)) @ R
+        elif kind == LIGHT_POINT:
+            xyz = (xyz - tr) @ R
+        elif kind != LIGHT_AMBIENT:
+            raise ValueError(f"light {i}: kind must be 0 (ambient), 1 (directional) or 2 (point), got {kind!r}")
+        rows[i, 0], rows[i, 1:4], rows[i, 4:7] = kind, xyz, np.asarray(rgb, np.float64)
+    return rows
+
+
+def view_tables(assets, requests, H, W, lights=None):
+    """the per-view tables of sections RD and RS, plus what the files need -> (tables, per-view extras).  lights: world-space rows
+    like REFERENCE_LIGHTS (the default), at most MAX_LIGHTS"""
+    lights = REFERENCE_LIGHTS if lights is None else tuple(lights)
+    if len(lights) > MAX_LIGHTS:
+        raise ValueError(f"{len(lights)} lights, the table holds at most {MAX_LIGHTS}")
     V = len(requests)
     used = [assets[r.asset] for r in requests]
     M = max([len(a.visual_link) for a in used] + [1])
     L = max([len(a.links) for a in used] + [1])
     t = dict(view_asset=np.asarray([r.asset for r in requests], np.int32).reshape(V), cam=np.zeros((V, CAM_DOUBLES)),
              vis_mat=np.zeros((V, M, 12)), link_cat=np.full((V, L), -1, np.int32), link_rank=np.full((V, L), -1, np.int32),
-             link_frame=np.zeros((V, L, FRAME_DOUBLES)), Nt_max=max([len(a.tris) for a in used] + [0]), H=int(H), W=int(W))
+             link_frame=np.zeros((V, L, FRAME_DOUBLES)), lights=np.zeros((V, len(lights), LIGHT_DOUBLES)),
+             Nt_max=max([len(a.tris) for a in used] + [0]), H=int(H), W=int(W))
     t['link_frame'][:, :, 3] = 1.0
     light = np.asarray(LIGHT_WORLD, np.float64) / np.linalg.norm(LIGHT_WORLD)
     extras = []
@@ -457,6 +684,7 @@ def view_tables(assets, requests, H, W):
         t['cam'][v, 4:13] = R.reshape(-1)
         t['cam'][v, 13:16] = tr
         t['cam'][v, 16:19] = light @ R
+        t['lights'][v] = light_rows(lights, R, tr)
         w2c = np.eye(4)
         w2c[:3, :3] = R.T
         w2c[:3, 3] = -(R.T @ tr)
@@ -483,9 +711,129 @@ def _edge(ax, ay, bx, by, px, py):
     return (bx - ax) * (py - ay) - (by - ay) * (px - ax)
 
 
-def render_tables_numpy(g, t):
+def shade_tables_numpy(g, t, out):
+    """section RS on the host, vectorised over the drawn pixels of a view: the same operation order in float64 as the kernel, so
+    the bytes agree.  Overwrites out['rgb'] from out['tri'] and out['depth']."""
+    check_texture_tables(g)
+    V, H, W = len(t['view_asset']), t['H'], t['W']
+    M = t['vis_mat'].shape[1]
+    A, Nt, Nv = len(g['assets']), len(g['tris']), len(g['verts'])
+    T = len(g['tex_table']) if g.get('tex_table') is not None else 0
+    if t['lights'].shape[1] > MAX_LIGHTS:
+        raise ValueError(f"{t['lights'].shape[1]} lights, the table holds at most {MAX_LIGHTS}")
+    bg = np.asarray(t.get('background', BACKGROUND_RGB), np.uint8)
+    ys, xs = np.mgrid[0:H, 0:W]
+    for v in range(V):
+        a = int(t['view_asset'][v])
+        first, count, nvis, _ = (int(x) for x in g['assets'][a]) if 0 <= a < A else (0, 0, 0, 0)
+        if first < 0 or count < 0 or first > Nt or count > Nt - first:
+            count = 0
+        count = min(count, t['Nt_max'])
+        rgb = np.empty((H, W, 3), np.uint8)
+        rgb[:] = bg
+        win = out['tri'][v].astype(np.int64)
+        hit = (win >= first) & (win < first + count)
+        if hit.any():
+            cam = t['cam'][v]
+            fx, fy, cx, cy = cam[:4]
+            tri_ids, inv = np.unique(win[hit], return_inverse=True)
+            tr, vis = g['tris'][tri_ids].astype(np.int64), g['tri_visual'][tri_ids].astype(np.int64)
+            ok = ~((vis < 0) | (vis >= M) | (vis >= nvis) | (tr < 0).any(1) | (tr >= Nv).any(1))
+            tr, vis = np.where(ok[:, None], tr, 0), np.where(ok, vis, 0)
+            m = t['vis_mat'][v][vis].reshape(-1, 1, 3, 4)
+            p = g['verts'][tr].astype(np.float64)
+            x, y, z = p[..., 0:1], p[..., 1:2], p[..., 2:3]
+            P = ((m[..., 0] * x + m[..., 1] * y) + m[..., 2] * z) + m[..., 3]  # [n,3 vertices,3 rows]
+            with np.errstate(all='ignore'):
+                ok &= (P[..., 2] >= NEAR).all(1)
+                su = np.rint(((fx * P[..., 0]) / P[..., 2] + cx) * 256.0)
+                sv = np.rint(((fy * P[..., 1]) / P[..., 2] + cy) * 256.0)
+                ok &= ((np.abs(su) <= GUARD) & (np.abs(sv) <= GUARD)).all(1)
+            X = np.where(ok[:, None], su, 0).astype(np.int64)
+            Y = np.where(ok[:, None], sv, 0).astype(np.int64)
+            area2 = _edge(X[:, 0], Y[:, 0], X[:, 1], Y[:, 1], X[:, 2], Y[:, 2])
+            ok &= area2 != 0
+            # per pixel from here on
+            ok, P, X, Y, flip, tid = ok[inv], P[inv], X[inv], Y[inv], (area2 < 0)[inv], tri_ids[inv]
+            sx, sy = xs[hit].astype(np.int64) * 256, ys[hit].astype(np.int64) * 256
+            x1, y1 = np.where(flip, X[:, 2], X[:, 1]), np.where(flip, Y[:, 2], Y[:, 1])
+            x2, y2 = np.where(flip, X[:, 1], X[:, 2]), np.where(flip, Y[:, 1], Y[:, 2])
+            z1, z2 = np.where(flip, P[:, 2, 2], P[:, 1, 2]), np.where(flip, P[:, 1, 2], P[:, 2, 2])
+            e0, e1, e2 = _edge(x1, y1, x2, y2, sx, sy), _edge(x2, y2, X[:, 0], Y[:, 0], sx, sy), _edge(X[:, 0], Y[:, 0], x1, y1, sx, sy)
+            with np.errstate(all='ignore'):
+                a2 = ((e0 + e1) + e2).astype(np.float64)
+                w0 = (e0.astype(np.float64) / a2) * (1.0 / P[:, 0, 2])
+                w1 = (e1.astype(np.float64) / a2) * (1.0 / z1)
+                w2 = (e2.astype(np.float64) / a2) * (1.0 / z2)
+                ws = (w0 + w1) + w2
+                b0, bo1, bo2 = w0 / ws, w1 / ws, w2 / ws
+                b1, b2 = np.where(flip, bo2, bo1), np.where(flip, bo1, bo2)
+                alb = g['tri_color'][tid].astype(np.float64) * 255.0
+                if T:
+                    tx = g['tri_tex'][tid].astype(np.int64)
+                    uv = g['tri_uv'][tid].astype(np.float64)  # [N,3,2]
+                    use = (tx >= 0) & (tx < T) & np.isfinite(uv).all(axis=(1, 2))
+                    row = g['tex_table'][np.where(use, tx, 0)].astype(np.int64)
+                    t0, tw, th = row[:, 0], row[:, 1], row[:, 2]
+                    tu = (b0 * uv[:, 0, 0] + b1 * uv[:, 1, 0]) + b2 * uv[:, 2, 0]
+                    tv = (b0 * uv[:, 0, 1] + b1 * uv[:, 1, 1]) + b2 * uv[:, 2, 1]
+                    fv = 1.0 - tv
+                    uu, vv = tu - np.floor(tu), fv - np.floor(fv)
+                    use &= (uu >= 0.0) & (uu <= 1.0) & (vv >= 0.0) & (vv <= 1.0)
+                    uu, vv = np.where(use, uu, 0.0), np.where(use, vv, 0.0)
+                    Xc, Yc = uu * tw.astype(np.float64) - 0.5, vv * th.astype(np.float64) - 0.5
+                    fi, fk = np.floor(Xc), np.floor(Yc)
+                    fxx, fyy = Xc - fi, Yc - fk
+                    i0, i1 = fi.astype(np.int64) % tw, (fi.astype(np.int64) + 1) % tw
+                    k0, k1 = fk.astype(np.int64) % th, (fk.astype(np.int64) + 1) % th
+                    tex = g['tex_data'].reshape(-1, 4)
+                    a00, a01 = tex[t0 + k0 * tw + i0, :3].astype(np.float64), tex[t0 + k0 * tw + i1, :3].astype(np.float64)
+                    a10, a11 = tex[t0 + k1 * tw + i0, :3].astype(np.float64), tex[t0 + k1 * tw + i1, :3].astype(np.float64)
+                    fxx, fyy = fxx[:, None], fyy[:, None]
+                    sampled = (a00 * (1.0 - fxx) + a01 * fxx) * (1.0 - fyy) + (a10 * (1.0 - fxx) + a11 * fxx) * fyy
+                    alb = np.where(use[:, None], sampled, alb)
+                ea, eb = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
+                nx = ea[:, 1] * eb[:, 2] - ea[:, 2] * eb[:, 1]
+                ny = ea[:, 2] * eb[:, 0] - ea[:, 0] * eb[:, 2]
+                nz = ea[:, 0] * eb[:, 1] - ea[:, 1] * eb[:, 0]
+                nn = np.sqrt((nx * nx + ny * ny) + nz * nz)
+                lit = nn > 0.0
+                nx, ny, nz = nx / nn, ny / nn, nz / nn
+                back = (nx * P[:, 0, 0] + ny * P[:, 0, 1]) + nz * P[:, 0, 2] > 0.0
+                nx, ny, nz = np.where(back, -nx, nx), np.where(back, -ny, ny), np.where(back, -nz, nz)
+                zz = out['depth'][v][hit].astype(np.float64)
+                p0, p1 = ((xs[hit].astype(np.float64) - cx) * zz) / fx, ((ys[hit].astype(np.float64) - cy) * zz) / fy
+                inten = np.zeros((len(zz), 3))
+                for L in t['lights'][v]:
+                    kind, col = L[0], L[4:7]
+                    if kind == 0.0:
+                        inten = inten + col[None, :]
+                    elif kind == 1.0:
+                        nd = (nx * L[1] + ny * L[2]) + nz * L[3]
+                        mm = np.where(lit & (nd > 0.0), nd, 0.0)
+                        inten = np.where(lit[:, None], inten + col[None, :] * mm[:, None], inten)
+                    elif kind == 2.0:
+                        dx, dy, dz = L[1] - p0, L[2] - p1, L[3] - zz
+                        r2 = (dx * dx + dy * dy) + dz * dz
+                        rr = np.sqrt(r2)
+                        nd = ((nx * dx + ny * dy) + nz * dz) / rr
+                        mm = np.where(nd > 0.0, nd, 0.0)
+                        on = lit & (rr > 0.0)
+                        inten = np.where(on[:, None], inten + (col[None, :] * mm[:, None]) / r2[:, None], inten)
+                val = np.rint(alb * inten)
+                val = np.where(val >= 255.0, 255.0, np.where(val > 0.0, val, 0.0))
+            col = np.where(ok[:, None], val.astype(np.uint8), bg[None, :])
+            rgb[hit] = col
+        out['rgb'][v] = rgb
+    return out
+
+
+def render_tables_numpy(g, t, shading="flat"):
     """section RD on the host, vectorised over triangles (setup) and over each triangle's pixel box (raster) and over pixels
-    (annotate): the same operation order in float64, the same integers.  -> dict of the kernels' outputs."""
+    (annotate): the same operation order in float64, the same integers.  -> dict of the kernels' outputs.  shading "textured":
+    section RS replaces the rgb result (shade_tables_numpy)."""
+    if shading not in SHADINGS:
+        raise ValueError(f"shading must be one of {SHADINGS}, got {shading!r}")
     V, H, W = len(t['view_asset']), t['H'], t['W']
     L = t['link_cat'].shape[1]
     M = t['vis_mat'].shape[1]
@@ -612,36 +960,47 @@ def render_tables_numpy(g, t):
             col = g['tri_color'][first + win[hit]].astype(np.float64) * shade[win[hit]][:, None]
             rgb[hit] = np.clip(np.rint(col * 255.0), 0, 255).astype(np.uint8)
         out['rgb'][v] = rgb
-    return out
+    return shade_tables_numpy(g, t, out) if shading == "textured" else out
 
 
-def render_tables_hip(g, t, device):
-    """section RD on the GPU: uploads, one kernel batch, ONE device-to-host copy of every result"""
+def render_tables_hip(g, t, device, shading="flat"):
+    """section RD (and RS for shading "textured") on the GPU: uploads, one kernel batch, ONE device-to-host copy of every result"""
     import torch
     from .. import hip_ops
+    if shading not in SHADINGS:
+        raise ValueError(f"shading must be one of {SHADINGS}, got {shading!r}")
     dev = torch.device(device)
+    if shading == "textured":
+        check_texture_tables(g)  # on the host, before any upload: the launches need no device-side check
+    else:
+        g = {k: a for k, a in g.items() if k not in ('tri_uv', 'tri_tex', 'tex_table', 'tex_data')}
+        t = {k: a for k, a in t.items() if k != 'lights'}
 
     def up(a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
 
     gd = {k: up(a) for k, a in g.items()}
     td = {k: up(a) for k, a in t.items() if isinstance(a, np.ndarray)}
-    buf, layout = hip_ops.render_batch(gd, td, t['H'], t['W'], t['Nt_max'], t.get('background', BACKGROUND_RGB))
+    buf, layout = hip_ops.render_batch(gd, td, t['H'], t['W'], t['Nt_max'], t.get('background', BACKGROUND_RGB), shading=shading,
+                                       check_tables=False)
     host = buf.cpu()
     return {k: a.numpy() for k, a in hip_ops.render_fields(host, layout).items()}
 
 
-def render_views(assets, requests, H, W, device=None) -> List[RenderedView]:
+def render_views(assets, requests, H, W, device=None, shading="flat", lights=None) -> List[RenderedView]:
     """requests (RenderRequest: asset index, joint qpos, camera position) -> RenderedView each.  device None: cuda:0 when there
-    is one, else the numpy path; "cpu": the numpy path."""
+    is one, else the numpy path; "cpu": the numpy path.  shading "textured": rgb is the textured, lit image of section RS under
+    `lights` (world-space rows like REFERENCE_LIGHTS, the default); every other field is what "flat" gives."""
+    if shading not in SHADINGS:
+        raise ValueError(f"shading must be one of {SHADINGS}, got {shading!r}")
     if device is None:
         import torch
         device = 'cuda:0' if torch.cuda.is_available() else 'cpu'
     g = geometry_tables(assets)
-    t, extras = view_tables(assets, requests, H, W)
+    t, extras = view_tables(assets, requests, H, W, lights)
     if not requests:
         return []
-    o = render_tables_numpy(g, t) if str(device).startswith('cpu') else render_tables_hip(g, t, device)
+    o = render_tables_numpy(g, t, shading) if str(device).startswith('cpu') else render_tables_hip(g, t, device, shading)
     views = []
     for v, (r, ex) in enumerate(zip(requests, extras)):
         a = assets[r.asset]
@@ -702,11 +1061,13 @@ def read_id_list(path):
 
 
 def render_dataset(dataset, data_path, id_list, model_ids, views, save_path, camera_ranges=None, height=800, width=800, batch=16,
-                   seed=0, device=None, workers=8, echo=True):
+                   seed=0, device=None, workers=8, echo=True, shading="flat", max_texture_size=None):
     """every model x camera range x render index: `batch` views per kernel batch (only the assets a batch shows are put into its
     geometry tables), files written on host threads.  -> statistics (views, render_s, wall_s)"""
     if dataset not in ('partnet', 'akb48'):
         raise ValueError(f"dataset must be 'partnet' or 'akb48', got {dataset!r}")
+    if shading not in SHADINGS:
+        raise ValueError(f"shading must be one of {SHADINGS}, got {shading!r}")
     t_start = time.perf_counter()
     cats = read_id_list(id_list)
     rng = np.random.RandomState(seed)
@@ -717,7 +1078,7 @@ def render_dataset(dataset, data_path, id_list, model_ids, views, save_path, cam
             raise ValueError(f"model {mid} is not listed in {id_list}")
         cat = cats[mid]
         path = os.path.join(data_path, str(mid)) if dataset == 'partnet' else os.path.join(data_path, cat, str(mid))
-        assets.append(load_asset(path, base_link_name=base))
+        assets.append(load_asset(path, base_link_name=base, textures=shading == "textured", max_texture_size=max_texture_size))
         for ci, rg in enumerate((camera_ranges or {}).get(cat, [DEFAULT_CAMERA_RANGE])):
             for ri in range(views):
                 qpos = sample_qpos(assets[-1], rng)
@@ -733,7 +1094,7 @@ def render_dataset(dataset, data_path, id_list, model_ids, views, save_path, cam
             shown = sorted({r.asset for r, _ in chunk})
             local = [RenderRequest(shown.index(r.asset), r.joint_qpos, r.camera_pos) for r, _ in chunk]
             t0 = time.perf_counter()
-            out = render_views([assets[a] for a in shown], local, height, width, device=device)
+            out = render_views([assets[a] for a in shown], local, height, width, device=device, shading=shading)
             stats['render_s'] += time.perf_counter() - t0
             for (_, meta), view in zip(chunk, out):
                 name = f"{meta['category']}_{meta['model_id']}_{meta['camera_idx']}_{meta['render_idx']}"
@@ -762,13 +1123,17 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--save_path', required=True)
     ap.add_argument('--device', default=None, help='cuda:0 (default when present) or cpu (the numpy path)')
+    ap.add_argument('--shading', default='flat', choices=SHADINGS,
+                    help='flat: base colour under one directional light; textured: map_Kd textures under the reference\'s light rig')
+    ap.add_argument('--max_texture_size', type=int, default=None, help='box-downscale larger textures at load (textured only)')
     args = ap.parse_args(argv)
     ranges = None
     if args.camera_ranges:
         with open(args.camera_ranges) as fd:
             ranges = json.load(fd)
     stats = render_dataset(args.dataset, args.data_path, args.id_list, args.model_ids, args.views, args.save_path, ranges, args.height,
-                           args.width, args.batch, args.seed, args.device)
+                           args.width, args.batch, args.seed, args.device, shading=args.shading,
+                           max_texture_size=args.max_texture_size)
     print(json.dumps(stats))
     return 0
 

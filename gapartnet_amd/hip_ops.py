@@ -1508,13 +1508,78 @@ def render_max_links() -> int:
     return int(_C.lib().gpn_render_max_links())
 
 
-def render_batch(geom, views, H, W, Nt_max, background=(0, 0, 0), timings=None, buf=None):
+RENDER_SHADINGS = ("flat", "textured")
+
+
+def render_max_lights() -> int:
+    return int(_C.lib().gpn_render_max_lights())
+
+
+def render_shade(geom, views, depth, tri, rgb, H, W, Nt_max, background=(0, 0, 0), check_tables=True):
+    """textured, lit RGB for rendered views (include/gpn.h section RS): overwrites rgb [V,H,W,3] u8 from depth [V,H,W] f32 and
+    tri [V,H,W] i32 of render_batch.  geom as for render_batch plus, when the asset set has textures, tri_uv [Nt,3,2] f32, tri_tex
+    [Nt] i32, tex_table [T,4] i32 and tex_data [texels,4] u8; views plus lights [V,NL,8] f64.  check_tables: the
+    contents of tri_tex and tex_table are checked on the device first (one small host read BEFORE the launch); a caller that built
+    the tables on the host and checked them there passes False."""
+    verts, tris = _c(geom["verts"], torch.float32), _c(geom["tris"], torch.int32)
+    tri_visual, tri_color, assets = _c(geom["tri_visual"], torch.int32), _c(geom["tri_color"], torch.float32), _c(geom["assets"], torch.int32)
+    view_asset, cam, vis_mat = _c(views["view_asset"], torch.int32), _c(views["cam"], torch.float64), _c(views["vis_mat"], torch.float64)
+    if "lights" not in views:
+        raise _C.GpnError("render_shade: views has no lights [V,NL,8] table")
+    lights = _c(views["lights"], torch.float64)
+    depth, tri = _c(depth, torch.float32), _c(tri, torch.int32)
+    if rgb.dtype != torch.uint8 or not rgb.is_contiguous():
+        raise _C.GpnError("render_shade: rgb must be a contiguous uint8 tensor")
+    tensors = [verts, tris, tri_visual, tri_color, assets, view_asset, cam, vis_mat, lights, depth, tri, rgb]
+    V, H, W, Nt_max = int(view_asset.shape[0]), int(H), int(W), int(Nt_max)
+    Nv, Nt, A = int(verts.shape[0]), int(tris.shape[0]), int(assets.shape[0])
+    if tuple(verts.shape) != (Nv, 3) or tuple(tris.shape) != (Nt, 3) or tri_visual.numel() != Nt or tuple(tri_color.shape) != (Nt, 3) \
+            or tuple(assets.shape) != (A, 4):
+        raise _C.GpnError("render_shade: verts [Nv,3], tris [Nt,3], tri_visual [Nt], tri_color [Nt,3], assets [A,4]")
+    if cam.numel() != V * 20 or vis_mat.dim() != 3 or vis_mat.shape[0] != V or vis_mat.shape[2] != 12 or lights.dim() != 3 \
+            or lights.shape[0] != V or lights.shape[2] != 8:
+        raise _C.GpnError("render_shade: cam [V,20], vis_mat [V,M,12], lights [V,NL,8]")
+    if depth.numel() != V * H * W or tri.numel() != V * H * W or rgb.numel() != V * H * W * 3:
+        raise _C.GpnError("render_shade: depth / tri [V,H,W], rgb [V,H,W,3]")
+    M, NL = int(vis_mat.shape[1]), int(lights.shape[1])
+    tri_uv = tri_tex = tex_table = tex_data = None
+    T = texels = 0
+    if geom.get("tex_table") is not None and int(geom["tex_table"].shape[0]) > 0:
+        tri_uv, tri_tex = _c(geom["tri_uv"], torch.float32), _c(geom["tri_tex"], torch.int32)
+        tex_table, tex_data = _c(geom["tex_table"], torch.int32), geom["tex_data"]
+        T = int(tex_table.shape[0])
+        texels = tex_data.numel() // 4
+        if tri_uv.numel() != Nt * 6 or tri_tex.numel() != Nt or tuple(tex_table.shape) != (T, 4) or tex_data.dtype != torch.uint8 \
+                or tex_data.numel() % 4 or not tex_data.is_contiguous():
+            raise _C.GpnError("render_shade: tri_uv [Nt,3,2], tri_tex [Nt], tex_table [T,4], tex_data [texels,4]")
+        tensors += [tri_uv, tri_tex, tex_table, tex_data]
+    _dev(*tensors)
+    if T and check_tables and Nt:
+        tt = tex_table.to(torch.int64)
+        bad = torch.stack([((tri_tex < -1) | (tri_tex >= T)).any(),
+                           ((tt[:, 0] < 0) | (tt[:, 1] < 1) | (tt[:, 2] < 1) | (tt[:, 0] + tt[:, 1] * tt[:, 2] > texels)).any()]).tolist()
+        if bad[0]:
+            raise _C.GpnError(f"render_shade: bad argument: tri_tex outside [-1, {T})")
+        if bad[1]:
+            raise _C.GpnError(f"render_shade: bad argument: a tex_table row spans texels outside tex_data ({texels} texels)")
+    check(_C.lib().gpn_render_shade(ptr(verts), i32(Nv), ptr(tris), ptr(tri_visual), ptr(tri_color), i32(Nt), ptr(assets), i32(A),
+                                    ptr(view_asset), ptr(cam), ptr(vis_mat), i32(M), ptr(tri_uv), ptr(tri_tex), ptr(tex_table), i32(T),
+                                    ptr(tex_data), i64(texels), ptr(lights), i32(NL), ptr(depth), ptr(tri), i32(V), i32(H), i32(W),
+                                    i32(Nt_max), i32(background[0]), i32(background[1]), i32(background[2]), ptr(rgb), _stream()),
+          "gpn_render_shade")
+    return rgb
+
+
+def render_batch(geom, views, H, W, Nt_max, background=(0, 0, 0), timings=None, buf=None, shading="flat", check_tables=True):
     """V views of articulated assets -> depth, winning triangle, labels, NPCS and RGB (include/gpn.h section RD: setup, raster,
     annotate; no host read in between).  geom: verts [Nv,3] f32, tris [Nt,3] i32, tri_visual / tri_link [Nt] i32, tri_color [Nt,3]
     f32, assets [A,4] i32.  views: view_asset [V] i32, cam [V,20] f64, vis_mat [V,M,12] f64, link_cat / link_rank [V,L] i32,
     link_frame [V,L,13] f64.  -> (buffer, layout): every result in ONE device buffer (render_fields names them).  timings: a list
-    that receives (start, end) torch events around each of the three entry points.  buf: a uint8 device buffer of the layout's
-    size to write into (default: a new one)."""
+    that receives (start, end) torch events around each of the entry points.  buf: a uint8 device buffer of the layout's
+    size to write into (default: a new one).  shading "textured": render_shade runs as a fourth launch and overwrites the rgb
+    field of the same buffer (section RS; geom and views then also carry its tables)."""
+    if shading not in RENDER_SHADINGS:
+        raise _C.GpnError(f"render_batch: shading must be one of {RENDER_SHADINGS}, got {shading!r}")
     verts, tris = _c(geom["verts"], torch.float32), _c(geom["tris"], torch.int32)
     tri_visual, tri_link = _c(geom["tri_visual"], torch.int32), _c(geom["tri_link"], torch.int32)
     tri_color, assets = _c(geom["tri_color"], torch.float32), _c(geom["assets"], torch.int32)
@@ -1561,6 +1626,15 @@ def render_batch(geom, views, H, W, Nt_max, background=(0, 0, 0), timings=None, 
                                           i32(H), i32(W), i32(Nt_max), wsp, wsb, i32(background[0]), i32(background[1]),
                                           i32(background[2]), ptr(f["link_area"]), ptr(f["link_inst"]), ptr(f["sem"]), ptr(f["ins"]),
                                           ptr(f["npcs"]), ptr(f["rgb"]), _stream()), "gpn_render_annotate")
+    if shading == "textured":
+        a = b = None
+        if timings is not None:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+        render_shade(geom, views, f["depth"], f["tri"], f["rgb"], H, W, Nt_max, background, check_tables=check_tables)
+        if timings is not None:
+            b.record()
+            timings.append((a, b))
     return buf, layout
 
 

@@ -967,6 +967,45 @@ int gpn_render_annotate(const float* depth, const int32_t* tri, const int32_t* t
                         int32_t* ins, float* npcs, uint8_t* rgb, gpn_stream_t stream);
 
 /* ================================================================================================
+ * RS - textured, lit RGB for the views of section RD (shading = "textured"): one launch after gpn_render_annotate that overwrites
+ * the rgb field and nothing else.  One 256-lane workgroup per 16 x 16 tile per view, one pixel per lane; the view's light rows
+ * are read once per workgroup into LDS; no atomics, no workspace, every output byte is written exactly once.  Everything is
+ * float64 in the order written here and uses only + - * / sqrt floor rint, so a host restatement agrees to the byte.
+ * Extra geometry: tri_uv [Nt,3,2] f32 = the vt of each corner in parsed corner order (NaN where a corner has none); tri_tex [Nt]
+ *   i32 = row of tex_table, -1 for none; tex_table [T,4] i32 = (first texel, w, h, 0); tex_data [texels] u32, a texel is the bytes
+ *   r g b 255 in memory order (r = bits 0-7); texels < 2^31.  T == 0: tri_uv, tri_tex, tex_table and tex_data are not read.
+ * Per view: lights [V,NL,8] f64 in the camera frame of the view, NL <= gpn_render_max_lights() = 16; a row is kind | x y z | r g b
+ *   | pad.  Kind 0 ambient; kind 1 directional, x y z = the unit vector TOWARDS the light; kind 2 point, x y z = its position.
+ *   Rows of another kind are skipped.
+ * For pixel (x, y) of view v with t = tri[v,y,x] inside the view's asset (otherwise: the background colour):
+ *   corners: P[3] (camera space, parsed order) and the snapped screen corners exactly as gpn_render_setup computes them (one
+ *     shared device function); flip = the doubled area of the parsed order is negative, oriented corners (0,1,2) or (0,2,1).
+ *   barycentrics: E0, E1, E2 = the raster's edge functions at (256 x, 256 y) over the oriented corners, l_j = (double)E_j /
+ *     (double)((E0 + E1) + E2), w_j = l_j * (1 / Z_j), b_j = w_j / ((w0 + w1) + w2); b is mapped back to parsed order.
+ *   uv = (b0 uv0 + b1 uv1) + b2 uv2, each corner's f32 widened first.
+ *   albedo_c in 0 ... 255: (double)tri_color[t][c] * 255, unless tri_tex[t] names a texture and all six tri_uv values are finite:
+ *     u' = u - floor(u), v' = (1 - v) - floor(1 - v) (OBJ origin bottom-left, row 0 of the image is its top); X = u' w - 0.5,
+ *     i = floor(X), fx = X - i; Y = v' h - 0.5, k = floor(Y), fy = Y - k; columns i mod w and (i + 1) mod w, rows k mod h and
+ *     (k + 1) mod h (wrapping: i = -1 is w - 1); albedo_c = (a00 (1 - fx) + a01 fx)(1 - fy) + (a10 (1 - fx) + a11 fx) fy with
+ *     a[row][column].  A tri_tex outside [-1, T) or a table row whose span leaves tex_data counts as no texture.
+ *   normal: n = (P1 - P0) x (P2 - P0), nn = sqrt((nx nx + ny ny) + nz nz), n = n / nn, negated when (nx P0x + ny P0y) + nz P0z >
+ *     0 (two-sided, towards the camera).  nn == 0: only the ambient rows count.
+ *   pixel point: z = (double)depth, p = (((x - cx) z) / fx, ((y - cy) z) / fy, z) as in gpn_render_annotate.
+ *   intensity, rows in table order, I_c = 0 first: ambient I_c = I_c + col_c; directional m = max(0, (nx dx + ny dy) + nz dz),
+ *     I_c = I_c + col_c m; point D = L - p, r2 = (Dx Dx + Dy Dy) + Dz Dz, r = sqrt(r2), skipped when r == 0, m = max(0, ((nx Dx +
+ *     ny Dy) + nz Dz) / r), I_c = I_c + (col_c m) / r2.
+ *   rgb_c = rint(albedo_c * I_c) clamped to 0 ... 255.
+ * The tables live on the device, so the entry point checks what it can see (null pointers, NL, T, texels, sizes); the contents
+ * of tri_tex and tex_table are bounds-checked in the kernel (never a fault) and refused by the Python layer before the upload.
+ * ================================================================================================ */
+int gpn_render_max_lights(void);
+int gpn_render_shade(const float* verts, int Nv, const int32_t* tris, const int32_t* tri_visual, const float* tri_color, int Nt,
+                     const int32_t* assets, int A, const int32_t* view_asset, const double* cam, const double* vis_mat, int M,
+                     const float* tri_uv, const int32_t* tri_tex, const int32_t* tex_table, int T, const void* tex_data,
+                     int64_t texels, const double* lights, int NL, const float* depth, const int32_t* tri, int V, int H, int W,
+                     int Nt_max, int bg_r, int bg_g, int bg_b, uint8_t* rgb, gpn_stream_t stream);
+
+/* ================================================================================================
  * PF - pose fitting.  replaces the per-proposal numpy loop of gapartnet/misc/pose_fitting.py:4-147 (estimate_pose_from_npcs:
  * 5-point RANSAC over Umeyama similarity fits, Umeyama on the inliers, NPCS-aligned box; callers network/model.py:966-980,
  * structure/utils.py:172-188) for ALL proposals of a batch: two launches, float64 like the reference.
