@@ -18,7 +18,7 @@ _SIZE_T_FUNCS = (
     "gpn_rulebook_down_lists_ws_bytes", "gpn_rulebook_level_counts_ws_bytes", "gpn_spconv_fwd_ws_bytes", "gpn_spconv_fwd_w_ws_bytes", "gpn_net_ws_bytes", "gpn_linear_bwd_ws_bytes", "gpn_ball_query_grid_ws_bytes", "gpn_point_losses_ws_bytes", "gpn_rulebook_tile_order_ws_bytes", "gpn_bn_ws_bytes", "gpn_spconv_wgrad_ws_bytes", "gpn_ccl_ws_bytes", "gpn_nms_ws_bytes", "gpn_pn2_furthest_point_sampling_ws_bytes", "gpn_pose_fit_ws_bytes", "gpn_proposals_revoxelize_ws_bytes", "gpn_proposals_postprocess_ws_bytes", "gpn_backbone_prepare_arena_bytes", "gpn_scene_prepare_ws_bytes",
     "gpn_view_fps_ws_bytes", "gpn_net_forward_bf16_ws_bytes", "gpn_scene_maps_ws_bytes", "gpn_boxes_draw_ws_bytes",
     "gpn_pointmlp_wgrad_ws_bytes", "gpn_cloud_nearest_ws_bytes", "gpn_proposals_from_masks_ws_bytes",
-    "gpn_render_ws_bytes", "gpn_frame_select_ws_bytes",
+    "gpn_render_ws_bytes", "gpn_frame_select_ws_bytes", "gpn_ground_mask_resize_ws_bytes", "gpn_ground_knn_ws_bytes",
 )
 
 

@@ -53,6 +53,8 @@ const char* kEntryPoints[] = {
     "gpn_pose_gt_fit", "gpn_box_iou_3d", "gpn_pose_pair_errors",
     "gpn_render_max_links", "gpn_render_ws_bytes", "gpn_render_setup", "gpn_render_raster", "gpn_render_annotate",
     "gpn_render_max_lights", "gpn_render_shade",
+    "gpn_ground_mask_resize_ws_bytes", "gpn_ground_mask_resize", "gpn_ground_mask_pool", "gpn_ground_bank_norms",
+    "gpn_ground_knn_ws_bytes", "gpn_ground_knn",
     "gpn_last_error", "gpn_version"};
 }  // namespace
 

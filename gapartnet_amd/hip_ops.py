@@ -2189,3 +2189,99 @@ def pointmlp_wgrad(x, dy, cin, offsets=None, offsets_host=None, view=None, per_s
                                i64(S), i64(N), i32(cin), i32(cout), i32(bool(per_segment)), ptr(dw), ptr(db), ptr(ws), szt(ws.numel()),
                                _stream()), "gpn_pointmlp_wgrad")
     return dw, db
+
+
+# ---------------------------------------------------------------------------------------------------- GR (grounding)
+GROUND_MAX_K = 32
+GROUND_MAX_CLASSES = 64
+GROUND_MAX_SIDE = 4096
+_GROUND_TABLES = {}
+
+
+def ground_mask_resize(masks, size, tables):
+    """binary masks [K,H,W] u8 / bool (non-zero = member) -> levels [K,Hf,Wf] u8 in 0..128 (0 = inside): Pillow's 8-bit bicubic
+    resize of 128 (1 - m), byte for byte (include/gpn.h section GR).  ``size`` = (Hf, Wf); ``tables`` = (xbounds [Wf,2], xcoef
+    [Wf,ksx], ybounds [Hf,2], ycoef [Hf,ksy]) int32 numpy arrays, Pillow's coefficient tables (misc/grounding.py:
+    resample_tables).  They are uploaded once per (shape, device)."""
+    dev = _dev(masks)
+    if masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool):
+        raise _C.GpnError("ground_mask_resize: masks [K,H,W] of dtype uint8 or bool (float-valued masks are not supported)")
+    masks = masks.contiguous()
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    K, H, W = (int(v) for v in masks.shape)
+    Hf, Wf = int(size[0]), int(size[1])
+    xb, xc, yb, yc = (np.ascontiguousarray(t, dtype=np.int32) for t in tables)
+    if xb.shape != (Wf, 2) or yb.shape != (Hf, 2) or xc.ndim != 2 or yc.ndim != 2 or xc.shape[0] != Wf or yc.shape[0] != Hf:
+        raise _C.GpnError("ground_mask_resize: tables are (xbounds [Wf,2], xcoef [Wf,ksx], ybounds [Hf,2], ycoef [Hf,ksy])")
+    # (keyed by the caller's array objects, which the entry keeps alive: resample_tables hands out one tuple per shape)
+    key = (dev.index,) + tuple(id(t) for t in tables)
+    hit = _GROUND_TABLES.get(key)
+    if hit is None:
+        if len(_GROUND_TABLES) >= 64:  # (a caller that builds new tables every call must not grow the cache without bound)
+            _GROUND_TABLES.clear()
+        flat = np.concatenate([xb.reshape(-1), xc.reshape(-1), yb.reshape(-1), yc.reshape(-1)])
+        hit = _GROUND_TABLES[key] = (torch.from_numpy(flat).to(dev), tuple(tables))
+    tables_dev = hit[0]
+    levels = torch.empty((K, Hf, Wf), dtype=torch.uint8, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_ground_mask_resize_ws_bytes(i32(K), i32(H), i32(Wf)), dev)
+    hp = lambda a: _C.ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    check(L.gpn_ground_mask_resize(ptr(masks), i32(K), i32(H), i32(W), i32(Hf), i32(Wf), hp(xb), hp(xc), i32(xc.shape[1]), hp(yb),
+                                   hp(yc), i32(yc.shape[1]), ptr(tables_dev), ptr(levels), ptr(ws), szt(ws.numel()), _stream()),
+          "gpn_ground_mask_resize")
+    return levels
+
+
+def ground_mask_pool(feature_maps, levels, mask_view):
+    """feature_maps [V,Hf,Wf,C] f32, levels [K,Hf,Wf] u8 (0..128, 0 = inside), mask_view [K] (the map of each mask) -> feat [K,C]
+    f32 = max over the pixels of fea * ((128 - level) / 128), section GR"""
+    dev = _dev(feature_maps, levels, mask_view)
+    fea = _c(feature_maps, torch.float32)
+    levels, mask_view = _c(levels, torch.uint8), _c(mask_view, torch.int32)
+    if fea.dim() != 4 or levels.dim() != 3 or tuple(levels.shape[1:]) != tuple(fea.shape[1:3]) or mask_view.numel() != levels.shape[0]:
+        raise _C.GpnError("ground_mask_pool: feature_maps [V,Hf,Wf,C], levels [K,Hf,Wf] of the maps' size, mask_view [K]")
+    V, Hf, Wf, C = (int(v) for v in fea.shape)
+    K = int(levels.shape[0])
+    feat = torch.empty((K, C), dtype=torch.float32, device=dev)
+    check(_C.lib().gpn_ground_mask_pool(ptr(fea), ptr(levels), ptr(mask_view), i32(V), i32(Hf), i32(Wf), i32(C), i32(K), ptr(feat),
+                                        _stream()), "gpn_ground_mask_pool")
+    return feat
+
+
+def ground_bank_norms(bank):
+    """bank [M,D] f32 -> squared row norms [M] f32 (section GR; once per bank)"""
+    dev = _dev(bank)
+    bank = _c(bank, torch.float32)
+    if bank.dim() != 2:
+        raise _C.GpnError("ground_bank_norms: bank [M,D]")
+    norms = torch.empty((bank.shape[0],), dtype=torch.float32, device=dev)
+    check(_C.lib().gpn_ground_bank_norms(ptr(bank), i64(bank.shape[0]), i32(bank.shape[1]), ptr(norms), _stream()),
+          "gpn_ground_bank_norms")
+    return norms
+
+
+def ground_knn(queries, bank, bank_norms, bank_labels, k, n_classes):
+    """queries [Q,D], bank [M,D] f32 (contiguous), bank_norms [M] f32 (ground_bank_norms), bank_labels [M] i32 in [0, n_classes)
+    -> (nn_index [Q,k] i32 ascending by (d2, row), nn_d2 [Q,k] f32, votes [Q,n_classes] i32, label [Q] i32), section GR.  The
+    labels are on the device and are not read here: a bank is checked once where it is built (misc/grounding.PartGrounder)."""
+    dev = _dev(queries, bank, bank_norms, bank_labels)
+    queries = _c(queries, torch.float32)
+    if (bank.dtype != torch.float32 or bank_norms.dtype != torch.float32 or bank_labels.dtype != torch.int32
+            or not (bank.is_contiguous() and bank_norms.is_contiguous() and bank_labels.is_contiguous())):
+        raise _C.GpnError("ground_knn: the bank is contiguous f32 [M,D] with f32 norms [M] and i32 labels [M]")
+    if queries.dim() != 2 or bank.dim() != 2 or queries.shape[1] != bank.shape[1] or bank_norms.numel() != bank.shape[0] \
+            or bank_labels.numel() != bank.shape[0]:
+        raise _C.GpnError("ground_knn: queries [Q,D], bank [M,D], bank_norms [M], bank_labels [M]")
+    Q, D, M, k, n_classes = int(queries.shape[0]), int(queries.shape[1]), int(bank.shape[0]), int(k), int(n_classes)
+    L = _C.lib()
+    # (bad k / M / D / n_classes: the library refuses them before any launch; outputs are sized only for sane values)
+    ks, cs = min(max(k, 0), GROUND_MAX_K), min(max(n_classes, 0), GROUND_MAX_CLASSES)
+    nn_index = torch.empty((Q, ks), dtype=torch.int32, device=dev)
+    nn_d2 = torch.empty((Q, ks), dtype=torch.float32, device=dev)
+    votes = torch.empty((Q, cs), dtype=torch.int32, device=dev)
+    label = torch.empty((Q,), dtype=torch.int32, device=dev)
+    ws = _ws(L.gpn_ground_knn_ws_bytes(i64(Q), i64(M), i32(k)), dev)
+    check(L.gpn_ground_knn(ptr(queries), i64(Q), ptr(bank), ptr(bank_norms), ptr(bank_labels), i64(M), i32(D), i32(k), i32(n_classes),
+                           ptr(nn_index), ptr(nn_d2), ptr(votes), ptr(label), ptr(ws), szt(ws.numel()), _stream()), "gpn_ground_knn")
+    return nn_index, nn_d2, votes, label

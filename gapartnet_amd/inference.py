@@ -18,6 +18,9 @@ end tools/visu_utils.py:141-173 ``OBJfile2points`` / ``FindMaxDis`` / ``WorldSpa
 ``python -m gapartnet_amd.inference --ckpt X --depth d.npy|d.png --rgb i.png --intrinsics K.txt|K.npy [--depth_scale 1000
         --keep_mask m.png --flip --presample 4 --seed 0 --masks a.npz] --out DIR``   writes DIR/<name>.npz and DIR/<name>_overlay.png
         (``--masks``: ``masks`` [K, H, W] and ``labels`` [K] per frame); frames of different sizes go in separate batches
+        ``--bank bank.npy --features f0.npy ...`` next to ``--masks``: class-agnostic masks (a segmenter's) - the ``.npz`` may omit
+        ``labels``; each mask's class is a 5-nearest-neighbour vote of its pooled image feature against the bank
+        (misc/grounding.py; csrc/ground.hip, include/gpn.h section GR) and the output gains ``mask_label_votes``
 
 CUDA tensors run on the HIP library; CPU tensors take the same graph in torch ops (FPS as a plain loop) - for tests and tiny
 inputs, never chosen for a CUDA tensor.
@@ -398,7 +401,7 @@ class FramePrediction:
     def to_numpy(self) -> dict:
         out = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items() if k != "masks"}
         if self.masks is not None:
-            out.update({"mask_" + f: v for f, v in self.masks.to_numpy().items() if f in MASK_FIELDS})
+            out.update({"mask_" + f: v for f, v in self.masks.to_numpy().items() if f in MASK_FIELDS or f == "label_votes"})
         return out
 
 
@@ -449,9 +452,12 @@ class MaskPrediction:
     sample_rows: torch.Tensor       # [m] i64
     sampled_points: torch.Tensor    # [m, C] f32, normalised frame
     sampled_sem: torch.Tensor       # [m] i64
+    label_votes: Optional[torch.Tensor] = None  # [K, n_classes] i32: the neighbours' votes behind ``label`` where a PartGrounder
+                                                # chose it (``predict_frames_with_masks`` with ``labels[v] = None``), else None
 
     def to_numpy(self) -> dict:
-        return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items()}
+        return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items()
+                if v is not None}
 
 
 def scene_maps_torch(valid_indices, sorted_indices, proposal_offsets, npcs_valid_mask, npcs_preds, n_rows):
@@ -720,6 +726,31 @@ class PartPredictor:
                                 bbox=boxes[v], box_proposal=p.box_proposal, corners_px=project_corners(boxes[v], K[v]),
                                 overlay=overlay[v], sample_rows=p.sample_rows) for v, p in enumerate(preds)]
 
+    @staticmethod
+    def _ground_labels(ask, labels, votes, masks, size, V, features, grounder):
+        """the frames ``ask`` of ``predict_frames_with_masks`` carry no labels: one ``PartGrounder.label_masks`` call over all their
+        masks (``mask_view`` = the frame's place among the asked ones) -> (labels, votes) with those frames filled in"""
+        from ._C import GpnError
+        if features is None or grounder is None:
+            raise GpnError(f"frames {ask} have no labels: pass features= (one feature map per frame) and grounder= (a PartGrounder)")
+        if len(features) != V:
+            raise GpnError(f"{V} frames need {V} feature maps, got {len(features)}")
+        dev = grounder.device
+        maps = [torch.as_tensor(features[v]).to(dev) for v in ask]
+        if any(m.dim() != 3 or m.shape != maps[0].shape for m in maps):
+            raise GpnError(f"feature maps must be [Hf, Wf, C] of one size, got {[tuple(m.shape) for m in maps]}")
+        counts = [int(torch.as_tensor(masks[v]).shape[0]) for v in ask]
+        with_masks = [torch.as_tensor(masks[v]).to(dev) for v, n in zip(ask, counts) if n]
+        stacked = torch.cat(with_masks) if with_masks else torch.zeros((0,) + tuple(size), dtype=torch.bool, device=dev)
+        view = torch.tensor([j for j, n in enumerate(counts) for _ in range(n)], dtype=torch.int32)
+        got = grounder.label_masks(torch.stack(maps), stacked, view)
+        labels, votes = list(labels), list(votes)
+        start = 0
+        for v, n in zip(ask, counts):
+            labels[v], votes[v] = got["label"][start:start + n], got["votes"][start:start + n]
+            start += n
+        return labels, votes
+
     @torch.no_grad()
     def predict_frames(self, depth, rgb, K, picks: Picks = None, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
                        flip: bool = False) -> List["FramePrediction"]:
@@ -736,7 +767,7 @@ class PartPredictor:
     @torch.no_grad()
     def predict_frames_with_masks(self, depth, rgb, K, masks: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], picks: Picks = None,
                                   min_points: int = 6, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
-                                  flip: bool = False) -> List["FramePrediction"]:
+                                  flip: bool = False, features=None, grounder=None) -> List["FramePrediction"]:
         """``predict_with_masks`` on frames: ``masks[v]`` [K_v, H, W] bool / u8 pixel masks (SAM's, or given ones;
         the reference's pixel_mask_to_point_mask), ``labels[v]`` [K_v] part classes.  Flattened, a pixel mask is a mask over the
         frame's rows.  -> ``FramePrediction`` per frame, its fields PER MASK in the caller's order where ``predict_frames`` has them
@@ -747,7 +778,14 @@ class PartPredictor:
         ``box_proposal`` = arange(K).  Masks may overlap, so there is no per-pixel part: ``instance`` is -1 and ``npcs`` zero
         everywhere (the members' NPCS are in ``masks.member_npcs``).  Host reads: 4, those of ``predict_with_masks`` - ONE for the
         preparation, the model's two (voxelisation, mask stage), ONE for the masks' sizes; nothing behind them has a
-        data-dependent size."""
+        data-dependent size.
+
+        Class-agnostic masks: ``labels[v] = None`` (or ``labels=None`` for every frame) with ``features`` - one image feature map
+        [Hf,Wf,C] per frame, all of one size - and ``grounder``, a ``misc.grounding.PartGrounder``: the masks of those frames are
+        labelled first (``PartGrounder.label_masks``, one call for all of them, no host read), ``masks.label`` /
+        ``proposal_classes`` are the chosen classes and ``masks.label_votes`` [K,n_classes] the neighbours' votes.  A call that
+        passes every label never touches ``features`` or ``grounder``.  (Masks on cloud rows, ``predict_with_masks``, have no pixel
+        grid to pool a feature map over: label those with ``PartGrounder.label_masks`` / ``.predict`` on your own features.)"""
         depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
         V, H, W = (int(v) for v in depth.shape)
         flat = []
@@ -756,8 +794,15 @@ class PartPredictor:
             if mk.dim() != 3 or (mk.shape[0] and tuple(mk.shape[1:]) != (H, W)):
                 raise ValueError(f"frame {v}: masks must be [K, {H}, {W}], got {tuple(mk.shape)}")
             flat.append(mk.reshape(mk.shape[0], H * W))
+        labels = [None] * len(flat) if labels is None else list(labels)
+        votes = [None] * len(labels)
+        ask = [v for v, lab in enumerate(labels) if lab is None]
+        if ask:
+            labels, votes = self._ground_labels(ask, labels, votes, masks, (H, W), V, features, grounder)
         prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip)
         mp = self._predict_masks_prepared(prep, flat, labels, picks, min_points)
+        for p, vt in zip(mp, votes):
+            p.label_votes = vt
         dev = rgb.device
         unflip = torch.tensor([1.0, -1.0, -1.0] if flip else [1.0, 1.0, 1.0], dtype=torch.float64).to(dev, non_blocking=True)
         boxes = [p.bbox * unflip for p in mp]   # (NaN where not valid: drawn by nobody)
@@ -886,10 +931,23 @@ def _main_frames(ap, args, model, device) -> int:
         given = []
         for path, d in zip(args.masks, depth):
             z = np.load(path)
-            m, lab = np.asarray(z["masks"]) != 0, np.asarray(z["labels"]).astype(np.int64).reshape(-1)
+            m = np.asarray(z["masks"]) != 0
+            if "labels" not in z.files and args.bank is not None:  # class-agnostic masks: the bank labels them
+                if m.shape[1:] != d.shape:
+                    ap.error(f"{path}: `masks` must be [K, {d.shape[0]}, {d.shape[1]}], got {m.shape}")
+                given.append((m, None))
+                continue
+            lab = np.asarray(z["labels"]).astype(np.int64).reshape(-1)
             if m.shape != (lab.shape[0],) + d.shape:
                 ap.error(f"{path}: `masks` must be [K, {d.shape[0]}, {d.shape[1]}] with `labels` [K], got {m.shape} and {lab.shape}")
             given.append((m, lab))
+    grounder, fmaps = None, None
+    if args.bank is not None and any(lab is None for _, lab in given):
+        from .misc.grounding import PartGrounder, load_feature_bank
+        grounder = PartGrounder(*load_feature_bank(args.bank), device=device)
+        fmaps = [np.load(p).astype(np.float32) for p in args.features]
+        if any(f.ndim != 3 or f.shape != fmaps[0].shape for f in fmaps):
+            ap.error(f"--features: maps must be [Hf, Wf, C] of one size, got {[f.shape for f in fmaps]}")
     for d, c, p in zip(depth, rgb, args.rgb):
         if c.shape != d.shape + (3,):
             ap.error(f"{p}: the image must be [{d.shape[0]}, {d.shape[1]}, 3], got {c.shape}")
@@ -907,8 +965,11 @@ def _main_frames(ap, args, model, device) -> int:
         if given is None:
             got = predictor.predict_frames(stack(depth), stack(rgb), K, **kw)
         else:
+            if grounder is not None:
+                kw.update(features=[torch.from_numpy(fmaps[i]).to(device) for i in ids], grounder=grounder)
             got = predictor.predict_frames_with_masks(stack(depth), stack(rgb), K, [torch.from_numpy(given[i][0]).to(device) for i in ids],
-                                                      [torch.from_numpy(given[i][1]).to(device) for i in ids], **kw)
+                                                      [None if given[i][1] is None else torch.from_numpy(given[i][1]).to(device) for i in ids],
+                                                      **kw)
         for i, p in zip(ids, got):
             preds[i] = p
     from PIL import Image
@@ -944,9 +1005,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--no_flip", action="store_true", help="keep the y and z signs of .obj inputs")
     ap.add_argument("--masks", nargs="+", default=None,
                     help="one .npz per input, in order: `masks` [K, N] on the input's rows and `labels` [K] part classes")
+    ap.add_argument("--bank", default=None,
+                    help="frames with --masks: a bank of labelled part features (misc.grounding.load_feature_bank); the masks' "
+                         "`labels` may then be missing and are chosen by a 5-nearest-neighbour vote")
+    ap.add_argument("--features", nargs="+", default=None, help="with --bank: one image feature map [Hf, Wf, C] (.npy) per frame")
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
     args = ap.parse_args(argv)
     device = torch.device(args.device)
+    if (args.bank is None) != (args.features is None):
+        ap.error("--bank and --features are given together")
+    if args.bank is not None:
+        if args.depth is None or args.masks is None:
+            ap.error("--bank / --features label pixel masks: they go with --depth ... --masks")
+        if len(args.features) != len(args.depth):
+            ap.error(f"--features takes one feature map per frame ({len(args.depth)}), got {len(args.features)}")
     if args.panels and device.type != "cuda":
         ap.error("--panels renders on the GPU (misc/visu.render_panels): it cannot be combined with --device cpu")
     if (args.input is None) == (args.depth is None):

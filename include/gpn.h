@@ -1179,6 +1179,55 @@ int gpn_boxes_draw(const double* bbox, const int32_t* box_scene, int64_t Q, cons
                    uint8_t* canvas, void* ws, size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * GR - class labels for class-agnostic 2D masks ("grounding"): everything between "pixel masks + an image feature map" and "the
+ * part class of every mask".  Reference: structure/utils.py:491-497 (mask_change_reso), structure/gapartnet.py:145-158
+ * (mask_fea_process / sam_mask_fea_process), utils.py:499-528 (load_data_single_file, KNN_classifier), gapartnet.py:180-204
+ * (get_GAPart_grounding_result / get_sam_grounding_result).  The feature extractor and the segmenter are the caller's.  No float
+ * atomics, every reduction has a fixed shape, nothing is read back; a mask's or a query's result is bit-equal whatever else is in
+ * the call.  Counts of 0 (K, Q) are valid calls that launch nothing.
+ * gpn_ground_mask_resize: binary masks [K,H,W] u8 (non-zero = member) -> levels [K,Hf,Wf] u8 in 0..128 (0 = fully inside).  For a
+ *   0/1 mask the reference's detour (colour map -> PIL.Image.resize -> first channel -> clip(0,128)) is Pillow's default (bicubic)
+ *   resize of the 8-bit image 128 (1 - m), clipped to 0..128, and this is that resize byte for byte: a horizontal pass to a u8
+ *   intermediate [K,H,Wf] (the workspace), then a vertical pass, each out = clip8((2^21 + sum_j coef[j] * in[first + j]) >> 22) in
+ *   32-bit integers.  The coefficient tables are Pillow's (bicubic a = -0.5, support 2 max(1, in/out), normalised in double,
+ *   trunc(+-0.5 + w 2^22)); the caller computes them on the host: xbounds_host [Wf,2] i32 = (first, count), xcoef_host
+ *   [Wf,ksize_x] i32, the same for y, and tables_dev = the four arrays back to back on the device (xbounds | xcoef | ybounds |
+ *   ycoef).  The host copies are only checked (0 <= first, count <= ksize, first + count <= the input extent: GPN_ERR_ARG before
+ *   any launch), the kernels read tables_dev.  H, W, Hf, Wf <= GPN_GROUND_MAX_SIDE.  An equal size is the identity table, not a
+ *   special case.  Float-valued masks are not supported.
+ * gpn_ground_mask_pool: fea [V,Hf,Wf,C] f32, levels [K,Hf,Wf] u8, mask_view [K] i32 in 0..V-1 (clamped into it) -> feat [K,C] f32,
+ *   feat[k,c] = max over (h,w) of fea[mask_view[k],h,w,c] * ((128 - min(level,128)) / 128).  The weight is a multiple of 1/128, so
+ *   the one fp32 product is the only rounding.  A NaN product makes the result NaN (numpy's max); the sign of a zero result is
+ *   unspecified.  A map is read once per group of 8 consecutive masks that share its view.
+ * gpn_ground_bank_norms: bank [M,D] f32 -> norms [M] f32 = sum of squares (an fmaf chain per lane of a wave, then a shuffle tree).
+ *   Once per bank.
+ * gpn_ground_knn: queries [Q,D] f32, bank [M,D] f32, bank_norms [M], bank_labels [M] i32 -> nn_index [Q,k] i32 (ascending by
+ *   distance), nn_d2 [Q,k] f32, votes [Q,n_classes] i32, label [Q] i32: KNeighborsClassifier(n_neighbors = k, brute force,
+ *   uniform weights).kneighbors / .predict.  d2 = max(0, (|q|^2 + |b|^2) - 2 q.b) in fp32, the dot product an fmaf chain in a fixed
+ *   order on the fp32 MFMA: |d2 - true| <= (D + 3) 2^-24 (|q|^2 + |b|^2).  Order: (d2, bank row) ascending - equal distances put the
+ *   lower row first; equal votes give the smallest class id.  A NaN distance never becomes a neighbour; if fewer than k rows have
+ *   a comparable distance the tail is index -1, d2 = +inf, no vote.  1 <= k <= GPN_GROUND_MAX_K, k <= M, D >= 1, 1 <= n_classes <=
+ *   GPN_GROUND_MAX_CLASSES, else GPN_ERR_ARG before any launch.  bank_labels lives on the device and is not read by the host: a
+ *   label outside 0..n_classes-1 casts no vote here, and the Python wrapper (PartGrounder) refuses such a bank when it is built.
+ *   The bank is streamed once per tile of 64 queries: workgroups own slices of bank rows and a running top-k per query, a second
+ *   launch merges the slices (workspace: gpn_ground_knn_ws_bytes).
+ * ================================================================================================ */
+#define GPN_GROUND_MAX_K 32
+#define GPN_GROUND_MAX_CLASSES 64
+#define GPN_GROUND_MAX_SIDE 4096
+size_t gpn_ground_mask_resize_ws_bytes(int K, int H, int Wf);
+int gpn_ground_mask_resize(const uint8_t* masks, int K, int H, int W, int Hf, int Wf, const int32_t* xbounds_host,
+                           const int32_t* xcoef_host, int ksize_x, const int32_t* ybounds_host, const int32_t* ycoef_host, int ksize_y,
+                           const int32_t* tables_dev, uint8_t* levels, void* ws, size_t ws_bytes, gpn_stream_t stream);
+int gpn_ground_mask_pool(const float* fea, const uint8_t* levels, const int32_t* mask_view, int V, int Hf, int Wf, int C, int K,
+                         float* feat, gpn_stream_t stream);
+int gpn_ground_bank_norms(const float* bank, int64_t M, int D, float* norms, gpn_stream_t stream);
+size_t gpn_ground_knn_ws_bytes(int64_t Q, int64_t M, int k);
+int gpn_ground_knn(const float* queries, int64_t Q, const float* bank, const float* bank_norms, const int32_t* bank_labels, int64_t M,
+                   int D, int k, int n_classes, int32_t* nn_index, float* nn_d2, int32_t* votes, int32_t* label, void* ws,
+                   size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * DEV - entry points whose extents are DEVICE COUNTERS (round 4: the proposal stage of a training step without a host read;
  * reference glue: network/model.py:228-346, 348-462 - there every stage boundary is a device->host read of a size).
  * Convention of every *_dev entry point: an extent argument (N, P, M, V ...) is the BOUND its buffers are allocated for;
