@@ -23,9 +23,8 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kPer = 4;                    // pixels per thread: pixel = chunk * kChunk + e * kThreads + tid
 constexpr int kChunk = kThreads * kPer;
-constexpr int kPasses = 4;                 // 32-bit hash, 8 bits a pass
-constexpr int kBins = 256;
-static_assert(kBins == kThreads, "one histogram bin per thread in the resolve");
+constexpr int kPasses = kSelectPasses;     // 32-bit hash, 8 bits a pass (point_prims.h)
+constexpr int kBins = kSelectBins;
 
 struct FrameSel {  // per frame, written by fr_count_kernel
   uint32_t t;      // threshold: hashes below it are kept
@@ -33,20 +32,6 @@ struct FrameSel {  // per frame, written by fr_count_kernel
   int32_t keep_all;
   int32_t pad;
 };
-
-__device__ __forceinline__ uint32_t fr_mix(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-// the hash of section FR, cut to its top hash_bits bits (1 .. 32)
-__device__ __forceinline__ uint32_t fr_key(uint32_t seed, uint32_t pixel, int hash_bits) {
-  const uint32_t h = fr_mix(fr_mix(pixel + seed * 0x9E3779B9u) ^ seed);
-  return hash_bits >= 32 ? h : h >> (32 - hash_bits);
-}
 
 // ---- 1. back-projection: one workgroup per chunk of a frame ---------------------------------------------------------------------
 template <typename T>
@@ -91,27 +76,7 @@ __global__ __launch_bounds__(kThreads) void fr_backproject_kernel(const T* __res
 }
 
 // ---- 2. radix select ------------------------------------------------------------------------------------------------------------
-// the digits of the cap-th smallest hash that the first `npass` merged histograms fix (most significant first) and the rank left
-// inside them.  Every thread returns the same values.  hist [kPasses][kBins] of the frame.
-__device__ __forceinline__ void fr_resolve(const uint32_t* __restrict__ hist, int npass, int cap, int* wsum, int* sh, uint32_t* prefix_out,
-                                           int* k_out) {
-  uint32_t prefix = 0;
-  int k = cap;
-  for (int j = 0; j < npass; ++j) {
-    if (threadIdx.x == 0) { sh[0] = kBins - 1; sh[1] = 1; }  // (never read back unless the histogram is short of k)
-    const int h = (int)hist[j * kBins + threadIdx.x];
-    int total;
-    const int incl = block_scan<kWaves>(h, wsum, &total);  // (its barriers order the two writes to sh)
-    if (incl - h < k && k <= incl) { sh[0] = threadIdx.x; sh[1] = k - (incl - h); }
-    __syncthreads();
-    prefix = (prefix << 8) | (uint32_t)sh[0];
-    k = sh[1];
-    __syncthreads();
-  }
-  *prefix_out = prefix;
-  *k_out = k;
-}
-
+// (the resolve of the cap-th smallest hash from the merged histograms: select_resolve, point_prims.h)
 // pass j: the histogram of digit j over the valid pixels whose higher digits equal the resolved prefix
 __global__ __launch_bounds__(kThreads) void fr_hist_kernel(const uint8_t* __restrict__ valid, const int32_t* __restrict__ valid_counts,
                                                            const uint32_t* __restrict__ seeds, int64_t HW, int cap, int hash_bits,
@@ -124,7 +89,7 @@ __global__ __launch_bounds__(kThreads) void fr_hist_kernel(const uint8_t* __rest
   uint32_t* hist = hist_all + (int64_t)v * kPasses * kBins;
   uint32_t prefix;
   int k;
-  fr_resolve(hist, pass, cap, wsum, sh, &prefix, &k);
+  select_resolve<kWaves>(hist, pass, cap, wsum, sh, &prefix, &k);
   bins[tid] = 0;
   __syncthreads();
   const uint32_t seed = seeds[v];
@@ -133,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void fr_hist_kernel(const uint8_t* __rest
   for (int e = 0; e < kPer; ++e) {
     const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
     if (p >= HW || !valid[(int64_t)v * HW + p]) continue;
-    const uint32_t hq = fr_key(seed, (uint32_t)p, hash_bits);
+    const uint32_t hq = hash_key(seed, (uint32_t)p, hash_bits);
     if (pass == 0 || (hq >> (shift + 8)) == prefix) atomicAdd(&bins[(hq >> shift) & 255u], 1u);
   }
   __syncthreads();
@@ -152,14 +117,14 @@ __global__ __launch_bounds__(kThreads) void fr_count_kernel(const uint8_t* __res
   const bool keep_all = cap <= 0 || valid_counts[v] <= cap;
   uint32_t t = 0xffffffffu;
   int r = 0;
-  if (!keep_all) fr_resolve(hist_all + (int64_t)v * kPasses * kBins, kPasses, cap, wsum, sh, &t, &r);
+  if (!keep_all) select_resolve<kWaves>(hist_all + (int64_t)v * kPasses * kBins, kPasses, cap, wsum, sh, &t, &r);
   const uint32_t seed = seeds[v];
   int less = 0, eq = 0;
 #pragma unroll
   for (int e = 0; e < kPer; ++e) {
     const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
     if (p >= HW || !valid[(int64_t)v * HW + p]) continue;
-    const uint32_t hq = fr_key(seed, (uint32_t)p, hash_bits);
+    const uint32_t hq = hash_key(seed, (uint32_t)p, hash_bits);
     less += (keep_all || hq < t) ? 1 : 0;
     eq += (!keep_all && hq == t) ? 1 : 0;
   }
@@ -209,55 +174,35 @@ __global__ __launch_bounds__(kThreads) void fr_compact_kernel(const float* __res
                                                               const FrameSel* __restrict__ sel, const int32_t* __restrict__ chunk_base,
                                                               const int32_t* __restrict__ chunk_eqbase, int64_t n_bound,
                                                               float4* __restrict__ packed, int32_t* __restrict__ pix) {
-  __shared__ int weq[kPer][kWaves], wkeep[kPer][kWaves];
-  const int v = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int wcnt[kPer][kWaves];
+  const int v = blockIdx.y, tid = threadIdx.x;
   const FrameSel s = sel[v];
   const int64_t ci = (int64_t)v * gridDim.x + blockIdx.x;
-  const int base = chunk_base[ci], eqbase = chunk_eqbase[ci];
   const uint32_t seed = seeds[v];
-  const unsigned long long below = (1ull << lane) - 1ull;
   bool lessf[kPer], eqf[kPer], keptf[kPer];
   int rank[kPer];
 #pragma unroll
   for (int e = 0; e < kPer; ++e) {
     const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
     const bool ok = p < HW && valid[(int64_t)v * HW + p] != 0;
-    const uint32_t hq = fr_key(seed, (uint32_t)p, hash_bits);
+    const uint32_t hq = hash_key(seed, (uint32_t)p, hash_bits);
     lessf[e] = ok && (s.keep_all || hq < s.t);
     eqf[e] = ok && !s.keep_all && hq == s.t;
-    const unsigned long long b = __ballot(eqf[e]);
-    rank[e] = __popcll(b & below);
-    if (lane == 0) weq[e][wave] = __popcll(b);
   }
-  __syncthreads();
-  // (slots in pixel order: e first, then the wave, then the lane)
-  int eq_before = eqbase;
+  // (slots in pixel order: e first, then the wave, then the lane - ordered_ranks, point_prims.h)
+  ordered_ranks<kWaves, kPer>(eqf, wcnt, chunk_eqbase[ci], rank);
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) keptf[e] = lessf[e] || (eqf[e] && rank[e] < s.r);
+  ordered_ranks<kWaves, kPer>(keptf, wcnt, chunk_base[ci], rank);
 #pragma unroll
   for (int e = 0; e < kPer; ++e) {
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) eq_before += w < wave ? weq[e][w] : 0;
-    keptf[e] = lessf[e] || (eqf[e] && eq_before + rank[e] < s.r);
-    const unsigned long long b = __ballot(keptf[e]);
-    rank[e] = __popcll(b & below);
-    if (lane == 0) wkeep[e][wave] = __popcll(b);
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) eq_before += w >= wave ? weq[e][w] : 0;
-  }
-  __syncthreads();
-  int before = base;
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) before += w < wave ? wkeep[e][w] : 0;
-    const int64_t pos = (int64_t)before + rank[e];
+    const int64_t pos = rank[e];
     if (keptf[e] && pos < n_bound) {
       const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
       const float* q = rows + ((int64_t)v * HW + p) * 6;
       packed[(int64_t)v * n_bound + pos] = make_float4(q[0], q[1], q[2], 1e10f);
       pix[(int64_t)v * HW + pos] = (int)p;
     }
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) before += w >= wave ? wkeep[e][w] : 0;
   }
 }
 

@@ -1,6 +1,6 @@
-// point_prims.h — the building blocks the point front ends share (pointnet2.hip, viewprep.hip, cloudprep.hip, frameprep.hip):
-// the no-fma distance, workgroup integer scan / sum, the furthest-point-sampling candidate with its three reduction steps, and
-// the ball normalisation.  Every one of them is pinned bit for bit by the oracle; this is their only definition.
+// point_prims.h — the building blocks the point front ends share (pointnet2.hip, viewprep.hip, cloudprep.hip, frameprep.hip,
+// gridsample.hip): the no-fma distance, workgroup integer scan / sum, the seeded hash with the resolve step of its radix select,
+// ballot-ordered ranks, the furthest-point-sampling candidate with its three reduction steps, and the ball normalisation.  Every one of them is pinned bit for bit by the oracle; this is their only definition.
 #pragma once
 #include "gpn_common.h"
 
@@ -62,6 +62,73 @@ __device__ __forceinline__ int block_scan(int c, int* wsum, int* total) {
   __syncthreads();  // wsum is rewritten by the next call
   *total = tot;
   return before + incl;
+}
+
+// ---- seeded radix select (include/gpn.h sections FR and GS): the k smallest 64-bit keys (hash << 32) | item of a set -------------
+__device__ __forceinline__ uint32_t hash_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+// the hash of section FR, cut to its top hash_bits bits (1 .. 32)
+__device__ __forceinline__ uint32_t hash_key(uint32_t seed, uint32_t item, int hash_bits) {
+  const uint32_t h = hash_mix(hash_mix(item + seed * 0x9E3779B9u) ^ seed);
+  return hash_bits >= 32 ? h : h >> (32 - hash_bits);
+}
+
+constexpr int kSelectPasses = 4;  // 32-bit hash, 8 bits a pass
+constexpr int kSelectBins = 256;  // one histogram bin per thread of a 256-thread workgroup
+
+// the digits of the k-th smallest hash that the first `npass` merged histograms fix (most significant first) and the rank left
+// inside them.  Every thread returns the same values.  hist [kSelectPasses][kSelectBins] of the set; sh: 2 ints of LDS.
+template <int kWaves>
+__device__ __forceinline__ void select_resolve(const uint32_t* __restrict__ hist, int npass, int k, int* wsum, int* sh,
+                                               uint32_t* prefix_out, int* k_out) {
+  static_assert(kWaves * 64 == kSelectBins, "one histogram bin per thread in the resolve");
+  uint32_t prefix = 0;
+  for (int j = 0; j < npass; ++j) {
+    if (threadIdx.x == 0) { sh[0] = kSelectBins - 1; sh[1] = 1; }  // (never read back unless the histogram is short of k)
+    const int h = (int)hist[j * kSelectBins + threadIdx.x];
+    int total;
+    const int incl = block_scan<kWaves>(h, wsum, &total);  // (its barriers order the two writes to sh)
+    if (incl - h < k && k <= incl) { sh[0] = threadIdx.x; sh[1] = k - (incl - h); }
+    __syncthreads();
+    prefix = (prefix << 8) | (uint32_t)sh[0];
+    k = sh[1];
+    __syncthreads();
+  }
+  *prefix_out = prefix;
+  *k_out = k;
+}
+
+// A workgroup of kWaves waves holds kPer * 64 * kWaves slots, slot = e * 64 * kWaves + thread: the number of set flags in the
+// slots before each of this thread's kPer slots (slot order: e first, then the wave, then the lane), plus `base`; returns the
+// workgroup's count of set flags.  wcnt: LDS, free again when the call returns.
+template <int kWaves, int kPer>
+__device__ __forceinline__ int ordered_ranks(const bool (&f)[kPer], int (*wcnt)[kWaves] /* [kPer] */, int base, int (&rank)[kPer]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) {
+    const unsigned long long b = __ballot(f[e]);
+    rank[e] = __popcll(b & below);
+    if (lane == 0) wcnt[e][wave] = __popcll(b);
+  }
+  __syncthreads();
+  int before = base;
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) {
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) before += w < wave ? wcnt[e][w] : 0;
+    rank[e] += before;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) before += w >= wave ? wcnt[e][w] : 0;
+  }
+  __syncthreads();  // wcnt is rewritten by the next call
+  return before - base;
 }
 
 // ---- furthest point sampling: the candidate (running distance, point index) and its reduction ---------------------------------

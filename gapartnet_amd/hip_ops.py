@@ -1657,8 +1657,9 @@ def _cloud_args(points, offsets):
     return points, pitch, host, torch.tensor(host, dtype=torch.int64).to(dev, non_blocking=True)
 
 
-def cloud_prepare(points, offsets, m, max_groups=0):
-    """S ragged raw clouds -> the network's input (include/gpn.h section CP): gpn_cloud_pack, gpn_view_fps, gpn_cloud_finish, no
+def cloud_prepare(points, offsets, m, max_groups=0, sampler="fps", seeds=None, hash_bits=32):
+    """S ragged raw clouds -> the network's input (include/gpn.h section CP): gpn_cloud_pack, gpn_view_fps (or, ``sampler`` "grid",
+    gpn_cloud_grid_sample with one uint32 of ``seeds`` per cloud; the result gains ``level`` [S] i64 on the host), gpn_cloud_finish, no
     host read between them and ONE at the end (counts, status, scale).  points [M, C >= 3] f32 (xyz first; rows with a
     non-finite coordinate are skipped), offsets [S+1] on the host.
     -> dict: out [S, m, C] f32 (ball-normalised xyz + the other columns; rows past counts[s] zero), sample_rows [S, m] i32 (-1 past
@@ -1673,7 +1674,7 @@ def cloud_prepare(points, offsets, m, max_groups=0):
     if S > 0:
         check(_C.lib().gpn_cloud_pack(ptr(points), i64(M), i32(pitch), ptr(off_dev), i32(S), i64(nb), ptr(packed), ptr(rows),
                                       ptr(counts), ptr(status), _stream()), "gpn_cloud_pack")
-    return _sample_and_finish(points, pitch, off_dev, S, packed, rows, nb, counts, status, m, max_groups)
+    return _sample_and_finish(points, pitch, off_dev, S, packed, rows, nb, counts, status, m, max_groups, sampler, seeds, hash_bits)
 
 
 def cloud_finish(points, pitch, off_dev, rows, n_bound, counts, idx, status, m):
@@ -1692,23 +1693,67 @@ def cloud_finish(points, pitch, off_dev, rows, n_bound, counts, idx, status, m):
     return out, sample_rows, scale
 
 
-def _sample_and_finish(points, pitch, off_dev, S, packed, rows, n_bound, counts, status, m, max_groups):
-    """what follows the packing, for raw clouds (cloud_prepare) and frames (frame_prepare) alike: gpn_view_fps over ``packed``,
-    gpn_cloud_finish over ``rows`` [S, n_bound], then counts, status and scale in ONE copy to the host"""
+SAMPLERS = ("fps", "grid")
+
+
+def _seed_tensor(seeds, S, dev):
+    """[S] uint32 values as the int32 tensor the library reads"""
+    t = torch.as_tensor(np.asarray(seeds, dtype=np.int64).astype(np.uint32).view(np.int32).reshape(-1)).to(dev, non_blocking=True)
+    if t.shape[0] != S:
+        raise _C.GpnError(f"{S} clouds need {S} seeds, got {t.shape[0]}")
+    return t
+
+
+def cloud_grid_sample(packed, counts, status, seeds, m, hash_bits=32):
+    """the octree-cell sampler (include/gpn.h section GS) in the slot of view_fps: packed [S, n_bound, 4] f32 (not written), counts /
+    status [S] i32 as gpn_cloud_pack / gpn_frame_select write them (status: n < m becomes CLOUD_FEW), seeds [S] uint32 values
+    -> (idx [S, m] i32 ascending packed rows, level [S] i32 = the octree level used, -1 where nothing was sampled)"""
+    dev = _dev(packed, counts, status)
+    S, nb, _ = packed.shape
+    idx = torch.zeros((S, int(m)), dtype=torch.int32, device=dev)
+    level = torch.full((S,), -1, dtype=torch.int32, device=dev)
+    if S == 0:
+        return idx, level
+    seeds = _seed_tensor(seeds, S, dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_cloud_grid_sample_ws_bytes(i32(S), i64(nb)), dev)
+    check(L.gpn_cloud_grid_sample(ptr(packed), i64(nb), ptr(counts), ptr(status), ptr(seeds), i32(S), i32(m), i32(hash_bits), ptr(idx),
+                                  ptr(level), ptr(ws), szt(ws.numel()), _stream()), "gpn_cloud_grid_sample")
+    return idx, level
+
+
+def _sample_and_finish(points, pitch, off_dev, S, packed, rows, n_bound, counts, status, m, max_groups, sampler="fps", seeds=None,
+                       hash_bits=32):
+    """what follows the packing, for raw clouds (cloud_prepare) and frames (frame_prepare) alike: gpn_view_fps (``sampler`` "fps")
+    or gpn_cloud_grid_sample ("grid", one uint32 of ``seeds`` per cloud) over ``packed``, gpn_cloud_finish over ``rows``
+    [S, n_bound], then counts, status, scale and the grid sampler's level in ONE copy to the host"""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     dev = points.device
     # counts, status and scale share one buffer: one copy to the host
     tail = torch.zeros((S, 6), dtype=torch.float64, device=dev)
-    ints = tail[:, 4:].view(torch.int32)  # [S, 4] i32: column 0 counts, column 1 status
-    idx = view_fps(packed, counts, status, m, max_groups) if S > 0 else None
+    ints = tail[:, 4:].view(torch.int32)  # [S, 4] i32: column 0 counts, column 1 status, column 2 the grid sampler's level
+    level = None
+    if S == 0:
+        idx = None
+    elif sampler == "grid":
+        idx, level = cloud_grid_sample(packed, counts, status, [0] * S if seeds is None else seeds, m, hash_bits)
+    else:
+        idx = view_fps(packed, counts, status, m, max_groups)
     out, sample_rows, scale = cloud_finish(points, pitch, off_dev, rows, n_bound, counts, idx, status, m)
     if S > 0:
         tail[:, :4] = scale
         ints[:, 0] = counts
         ints[:, 1] = status
+        if level is not None:
+            ints[:, 2] = level
     host_tail = tail.cpu()
     host_ints = host_tail[:, 4:].view(torch.int32)
-    return dict(out=out, sample_rows=sample_rows, offsets=off_dev, counts_dev=counts, status_dev=status,
-                counts=host_ints[:, 0].long().clamp(max=m), status=host_ints[:, 1].long(), scale=host_tail[:, :4].clone())
+    got = dict(out=out, sample_rows=sample_rows, offsets=off_dev, counts_dev=counts, status_dev=status,
+               counts=host_ints[:, 0].long().clamp(max=m), status=host_ints[:, 1].long(), scale=host_tail[:, :4].clone())
+    if sampler == "grid":
+        got["level"] = host_ints[:, 2].long()
+    return got
 
 
 def cloud_nearest(points, offsets, sample_rows, counts, status, want_d2=False):
@@ -1788,9 +1833,10 @@ def frame_select(rows, valid, valid_counts, seeds, cap, hash_bits=32):
     return packed, pix, counts, status
 
 
-def frame_prepare(depth, rgb, K, m, cap, seeds, keep=None, depth_scale=1.0, flip=False, hash_bits=32, max_groups=0):
+def frame_prepare(depth, rgb, K, m, cap, seeds, keep=None, depth_scale=1.0, flip=False, hash_bits=32, max_groups=0, sampler="fps"):
     """V RGB-D frames of one size -> the network's input (include/gpn.h sections FR and CP): gpn_frame_backproject,
-    gpn_frame_select, gpn_view_fps over at most ``cap`` rows a frame, gpn_cloud_finish; no host read between them and ONE at the
+    gpn_frame_select, gpn_view_fps (``sampler`` "grid": gpn_cloud_grid_sample with the presample's seeds) over at most ``cap`` rows a
+    frame, gpn_cloud_finish; no host read between them and ONE at the
     end (counts, status, scale).  -> what cloud_prepare returns (a frame is the cloud of its H*W pixel rows; sample_rows are pixel
     indices), plus ``rows`` [V*H*W, 6] f32 and ``valid_counts`` [V] i32 on the device."""
     V, H, W = (int(v) for v in depth.shape)
@@ -1798,7 +1844,8 @@ def frame_prepare(depth, rgb, K, m, cap, seeds, keep=None, depth_scale=1.0, flip
     packed, pix, counts, status = frame_select(rows, valid, valid_counts, seeds, cap, hash_bits)
     off_dev = torch.tensor([v * H * W for v in range(V + 1)], dtype=torch.int64).to(rows.device, non_blocking=True)
     # (pix has the pitch H*W: gpn_cloud_finish bounds the row indices it reads by its n_bound)
-    got = _sample_and_finish(rows, 6, off_dev, V, packed, pix, H * W, counts, status, int(m), max_groups)
+    # (``hash_bits`` is the presample's: the grid sampler hashes with all 32 bits, as cloud_prepare does)
+    got = _sample_and_finish(rows, 6, off_dev, V, packed, pix, H * W, counts, status, int(m), max_groups, sampler, seeds)
     got.update(rows=rows, valid_counts=valid_counts)
     return got
 

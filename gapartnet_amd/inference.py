@@ -3,20 +3,22 @@ gapartnet/tools/visu.py:79-143 ``_inference_perception_model`` / ``inference_rea
 end tools/visu_utils.py:141-173 ``OBJfile2points`` / ``FindMaxDis`` / ``WorldSpaceToBallSpace``).
 
 ``prepare_clouds``   ragged raw clouds of any size, sensor NaNs included -> the network's input: valid rows, FPS down to
-                     ``num_points``, ball normalisation over the sampled points (csrc/cloudprep.hip; include/gpn.h section CP)
+                     ``num_points``, ball normalisation over the sampled points (csrc/cloudprep.hip; include/gpn.h section CP);
+                     ``sampler="grid"`` (here, in ``prepare_frames``, ``PartPredictor`` and ``--sampler``): the opt-in octree-cell
+                     sampler instead of FPS (csrc/gridsample.hip; section GS; ``grid_sample_rows`` is its contract in numpy)
 ``PartPredictor``    ``model(pcs)`` -> score filter + NMS -> per-point maps and one box per part (the kernels of the test epoch's
                      rendering) -> every row of the caller's cloud through its nearest sampled point (gpn_cloud_nearest)
 ``PartPredictor.predict_with_masks``  parts the CALLER found (point masks with a part class each, on the raw rows): NPCS, a score
                      and a 9-DoF box per mask (``GAPartNet.forward_with_masks``; csrc/proposals.hip section MP)
 ``read_obj_points``  the reference's OBJ reader
-``python -m gapartnet_amd.inference --ckpt X --input a.npy b.obj ... --out DIR [--num_points N] [--inference_dtype bf16]
+``python -m gapartnet_amd.inference --ckpt X --input a.npy b.obj ... --out DIR [--num_points N] [--sampler grid] [--inference_dtype bf16]
         [--panels] [--no_flip] [--masks a.npz b.npz ...]``   (``--masks``: parallel to ``--input``, each file ``masks`` [K, N] and
         ``labels`` [K]; the output gains the ``mask_*`` arrays and the panels draw the masks' boxes)
 ``prepare_frames`` / ``PartPredictor.predict_frames`` / ``predict_frames_with_masks``  the same from RGB-D frames: depth, image and
                      intrinsics in (the reference's ObjIns.get_pc / get_downsampled_pc), per-pixel parts, camera-frame boxes and the
                      image with the boxes drawn out (csrc/frameprep.hip; include/gpn.h section FR)
 ``python -m gapartnet_amd.inference --ckpt X --depth d.npy|d.png --rgb i.png --intrinsics K.txt|K.npy [--depth_scale 1000
-        --keep_mask m.png --flip --presample 4 --seed 0 --masks a.npz] --out DIR``   writes DIR/<name>.npz and DIR/<name>_overlay.png
+        --keep_mask m.png --flip --presample 4 --seed 0 --sampler grid --masks a.npz] --out DIR``   writes DIR/<name>.npz and DIR/<name>_overlay.png
         (``--masks``: ``masks`` [K, H, W] and ``labels`` [K] per frame); frames of different sizes go in separate batches
         ``--bank bank.npy --features f0.npy ...`` next to ``--masks``: class-agnostic masks (a segmenter's) - the ``.npz`` may omit
         ``labels``; each mask's class is a 5-nearest-neighbour vote of its pooled image feature against the bank
@@ -50,6 +52,7 @@ class PreparedClouds:
     offsets: List[int]          # [S+1]: the clouds' rows in ``source``
     source: torch.Tensor        # [M, C] f32: the caller's clouds, concatenated
     table: Optional[dict] = None  # device tables gpn_cloud_nearest reads (CUDA only)
+    level: Optional[torch.Tensor] = None  # [S] i64 (host), sampler "grid" only: the octree level used, -1 where a cloud was not sampled
 
 
 # ---------------------------------------------------------------------------------------------------- torch formulation (CPU)
@@ -84,15 +87,19 @@ def _fps_loop(xyz: np.ndarray, m: int) -> np.ndarray:
     return out
 
 
-def _prepare_cloud_torch(cloud: torch.Tensor, m: int):
-    """one cloud -> (status, normalised [m_s, C] f32, sample_rows [m_s] i64, scale [4] f64)"""
+def _prepare_cloud_torch(cloud: torch.Tensor, m: int, sampler: str = "fps", seed: int = 0):
+    """one cloud -> (status, normalised [m_s, C] f32, sample_rows [m_s] i64, scale [4] f64, the grid sampler's level or -1)"""
     C = cloud.shape[1]
     none = (torch.zeros((0, C), dtype=torch.float32), torch.zeros(0, dtype=torch.int64), torch.zeros(4, dtype=torch.float64))
     rows = torch.nonzero(torch.isfinite(cloud[:, :3]).all(1)).squeeze(1)
     n = int(rows.shape[0])
+    level = -1
     if n == 0:
-        return (CLOUD_EMPTY,) + none
-    if n > m:
+        return (CLOUD_EMPTY,) + none + (level,)
+    if n > m and sampler == "grid":
+        picked, level = grid_sample_rows(cloud[rows, :3].numpy(), m, seed)
+        rows = rows[torch.from_numpy(picked)]
+    elif n > m:
         rows = rows[torch.from_numpy(_fps_loop(cloud[rows, :3].numpy(), m))]
     p = cloud[rows, :3].double()
     c = (p.max(0)[0] + p.min(0)[0]) / 2
@@ -100,10 +107,10 @@ def _prepare_cloud_torch(cloud: torch.Tensor, m: int):
     r = torch.sqrt(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).max())
     scale = torch.cat([r[None], c])
     if not bool(r > 0):
-        return CLOUD_DEGENERATE, none[0], none[1], scale
+        return CLOUD_DEGENERATE, none[0], none[1], scale, level
     out = cloud[rows].clone()
     out[:, :3] = (d / r).float()
-    return CLOUD_OK, out, rows, scale
+    return CLOUD_OK, out, rows, scale, level
 
 
 def _nearest_torch(queries: torch.Tensor, samples: torch.Tensor, chunk: int = 4096) -> torch.Tensor:
@@ -144,17 +151,40 @@ def _prepared_from_tables(got, m: int, offsets: List[int], source: torch.Tensor)
     points = got["out"].reshape(counts.shape[0] * m, -1).index_select(0, take)
     sample_rows = got["sample_rows"].reshape(-1).index_select(0, take).long()
     table = dict(sample_rows=got["sample_rows"], counts=got["counts_dev"], status=got["status_dev"])
-    return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, source, table)
+    return PreparedClouds(points, counts, sample_rows, got["scale"], status, offsets, source, table, got.get("level"))
 
 
-def prepare_clouds(clouds: Sequence[torch.Tensor], num_points: int = 20000, max_groups: int = 0) -> PreparedClouds:
+def _prepared_from_parts(parts, offsets: List[int], source: torch.Tensor, sampler: str) -> PreparedClouds:
+    """the per-cloud results of ``_prepare_cloud_torch`` as a ``PreparedClouds`` over ``source``"""
+    level = torch.tensor([p[4] for p in parts], dtype=torch.int64) if sampler == "grid" else None
+    return PreparedClouds(torch.cat([p[1] for p in parts]), torch.tensor([p[1].shape[0] for p in parts], dtype=torch.int64),
+                          torch.cat([p[2] for p in parts]), torch.stack([p[3] for p in parts]),
+                          torch.tensor([p[0] for p in parts], dtype=torch.int64), offsets, source, None, level)
+
+
+SAMPLERS = ("fps", "grid")
+
+
+def _check_sampler(sampler: str) -> str:
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    return sampler
+
+
+def prepare_clouds(clouds: Sequence[torch.Tensor], num_points: int = 20000, max_groups: int = 0, sampler: str = "fps",
+                   seed=0) -> PreparedClouds:
     """``clouds``: [N_i, C] float32 tensors, xyz first, any N_i (0 included); rows with a non-finite coordinate are skipped.  A cloud
     with more than ``num_points`` valid rows is sampled by FPS, a smaller one keeps every valid row; centre and radius of the ball
-    normalisation are those of the SAMPLED points, as in the converter the training data came from."""
+    normalisation are those of the SAMPLED points, as in the converter the training data came from.  ``sampler`` "grid" (opt-in):
+    the octree-cell sampler of include/gpn.h section GS instead of FPS - a sort and a few passes instead of ``num_points``
+    sequential steps, a coarser cover (the checkpoints were trained on FPS samples); ``seed``: one uint32 per cloud, or an int s for
+    s, s + 1, ...; the result's ``level`` is the octree level of every cloud."""
     clouds = _check_clouds(clouds)
+    _check_sampler(sampler)
     m = int(num_points)
     if m < 1:
         raise ValueError("num_points must be positive")
+    seeds = _frame_seeds(seed, len(clouds))
     offsets = [0]
     for c in clouds:
         offsets.append(offsets[-1] + int(c.shape[0]))
@@ -164,11 +194,8 @@ def prepare_clouds(clouds: Sequence[torch.Tensor], num_points: int = 20000, max_
         hip = backend.raw()
         if hip.name != "hip":
             raise RuntimeError("prepare_clouds on GPU tensors needs the HIP library as the operator backend")
-        return _prepared_from_tables(hip.cloud_prepare(source, offsets, m, max_groups), m, offsets, source)
-    parts = [_prepare_cloud_torch(c, m) for c in clouds]
-    return PreparedClouds(torch.cat([p[1] for p in parts]), torch.tensor([p[1].shape[0] for p in parts], dtype=torch.int64),
-                          torch.cat([p[2] for p in parts]), torch.stack([p[3] for p in parts]),
-                          torch.tensor([p[0] for p in parts], dtype=torch.int64), offsets, source)
+        return _prepared_from_tables(hip.cloud_prepare(source, offsets, m, max_groups, sampler=sampler, seeds=seeds), m, offsets, source)
+    return _prepared_from_parts([_prepare_cloud_torch(c, m, sampler, seeds[i]) for i, c in enumerate(clouds)], offsets, source, sampler)
 
 
 def nearest_samples(prep: PreparedClouds) -> torch.Tensor:
@@ -210,6 +237,46 @@ def select_pixels(valid_pixels: np.ndarray, seed: int, cap: int, hash_bits: int 
         return pix
     key = (frame_hash(seed, pix, hash_bits).astype(np.uint64) << np.uint64(32)) | pix.astype(np.uint64)
     return np.sort(pix[np.argsort(key, kind="stable")[:cap]])
+
+
+def grid_sample_rows(xyz: np.ndarray, m: int, seed: int = 0, hash_bits: int = 32):
+    """the octree-cell sampler on the host (include/gpn.h section GS): of the n rows of ``xyz`` [n, 3] f32 (all finite) -> (the m
+    chosen rows ascending i64, the octree level L*); n <= m: (every row, -1)"""
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32)[:, :3])
+    n, m = xyz.shape[0], int(m)
+    if n <= m:
+        return np.arange(n, dtype=np.int64), -1
+    q = np.zeros((n, 3), dtype=np.uint32)
+    with np.errstate(all="ignore"):
+        lo, hi = xyz.min(0), xyz.max(0)
+        e = np.float32((hi - lo).max())
+        if e > 0 and np.isfinite(e):
+            x = (xyz - lo) * np.float32(1024.0 / np.float64(e))
+            q = np.where(x < np.float32(1023.0), x, np.float32(1023.0)).astype(np.uint32)  # (a NaN, 0 * inf, takes 1023)
+    code = np.zeros(n, dtype=np.uint32)
+    for i in range(10):
+        for a in range(3):
+            code |= ((q[:, a] >> np.uint32(i)) & np.uint32(1)) << np.uint32(3 * i + a)
+    order = np.argsort(code, kind="stable")  # by (code, row): the order of the keys code << 32 | row
+    sc = code[order].astype(np.int64)
+    # the first level at which a sorted row opens a new cell: cells of level L differ when a bit >= 30 - 3 L of the codes differs
+    d = sc[1:] ^ sc[:-1]
+    top = np.floor(np.log2(np.maximum(d, 1))).astype(np.int64)
+    first = np.concatenate([[0], np.where(d == 0, 11, 10 - top // 3)])
+    cells = np.cumsum(np.bincount(first, minlength=12))[:11]  # C_0 .. C_10
+    L = int(np.nonzero(cells <= m)[0].max())
+    r = m - int(cells[L])
+    chosen = [order[first <= L]]  # stage A: a cell's first row in key order
+    if r > 0:
+        if L < 10:  # the level-(L+1) cells without a stage-A point, by (hash(cell), cell); each gives its first row
+            pos = np.nonzero(first == L + 1)[0]
+            item = sc[pos] >> (30 - 3 * (L + 1))
+        else:       # the rows stage A left, by (hash(row), row)
+            pos = np.nonzero(first == 11)[0]
+            item = order[pos].astype(np.int64)
+        key = (frame_hash(seed, item, hash_bits).astype(np.uint64) << np.uint64(32)) | item.astype(np.uint64)
+        chosen.append(order[pos[np.argsort(key, kind="stable")[:r]]])
+    return np.sort(np.concatenate(chosen)).astype(np.int64), L
 
 
 def _frame_seeds(seed, V: int) -> List[int]:
@@ -266,19 +333,22 @@ def _check_frames(depth, rgb, K, keep):
 
 
 def prepare_frames(depth, rgb, K, num_points: int = 20000, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
-                   flip: bool = False, hash_bits: int = 32, max_groups: int = 0) -> PreparedClouds:
+                   flip: bool = False, hash_bits: int = 32, max_groups: int = 0, sampler: str = "fps") -> PreparedClouds:
     """V RGB-D frames of one size -> the network's input (include/gpn.h section FR; the reference's ObjIns.get_pc /
     get_downsampled_pc, structure/gapartnet.py:541-627).  ``depth`` [V,H,W] f32 / f64 / u16 (divided by ``depth_scale``), ``rgb``
     [V,H,W,3] u8, ``K`` [V,3,3] or [3,3] (host data), ``keep`` [V,H,W] or None.  Every pixel becomes a row [x y z r g b] (NaN xyz
     where there is no depth); a frame with more than ``presample * num_points`` valid pixels is cut to that many by the seeded
     hash rule (``seed``: one uint32 per frame, or an int s for s, s + 1, ...; ``presample`` 0: no cut), then FPS and the ball
-    normalisation of ``prepare_clouds``.  The result's ``source`` is the [V*H*W, 6] rows, its ``sample_rows`` are pixel indices."""
+    normalisation of ``prepare_clouds``.  The result's ``source`` is the [V*H*W, 6] rows, its ``sample_rows`` are pixel indices.
+    ``sampler`` "grid": ``prepare_clouds``' octree-cell sampler behind the (unchanged) presample, with the frames' seeds."""
     depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
-    return _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits, max_groups)
+    return _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits, max_groups, sampler)
 
 
-def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits=32, max_groups=0):
+def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits=32, max_groups=0,
+                            sampler="fps"):
     """``prepare_frames`` behind its argument check (``_check_frames``), which the predictor's frame entries run themselves"""
+    _check_sampler(sampler)
     V, H, W = (int(v) for v in depth.shape)
     m, cap = int(num_points), int(presample) * int(num_points)
     if m < 1 or cap < 0:
@@ -291,7 +361,7 @@ def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, de
         if hip.name != "hip":
             raise RuntimeError("prepare_frames on GPU tensors needs the HIP library as the operator backend")
         got = hip.frame_prepare(depth, rgb, K.to(depth.device, non_blocking=True), m, cap, seeds, keep=keep, depth_scale=depth_scale, flip=flip,
-                                hash_bits=hash_bits, max_groups=max_groups)
+                                hash_bits=hash_bits, max_groups=max_groups, sampler=sampler)
         return _prepared_from_tables(got, m, offsets, got["rows"])
     d = depth.numpy()
     rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), K.numpy(),
@@ -302,10 +372,8 @@ def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, de
         drop = np.ones(H * W, dtype=bool)
         drop[select_pixels(np.nonzero(valid[v])[0], seeds[v], cap, hash_bits)] = False
         frame[drop, :3] = np.nan
-        parts.append(_prepare_cloud_torch(torch.from_numpy(frame), m))
-    return PreparedClouds(torch.cat([p[1] for p in parts]), torch.tensor([p[1].shape[0] for p in parts], dtype=torch.int64),
-                          torch.cat([p[2] for p in parts]), torch.stack([p[3] for p in parts]),
-                          torch.tensor([p[0] for p in parts], dtype=torch.int64), offsets, torch.from_numpy(rows))
+        parts.append(_prepare_cloud_torch(torch.from_numpy(frame), m, sampler, seeds[v]))
+    return _prepared_from_parts(parts, offsets, torch.from_numpy(rows), sampler)
 
 
 # the box edges of draw_bbox (structure/utils.py:73-89; include/gpn.h section VS): (corner a, corner b, colour as written, thickness)
@@ -525,8 +593,9 @@ class PartPredictor:
     ``picks``: the RANSAC draws of the box fits - None (drawn from numpy's global generator), a tensor [kept proposals,
     max_iters, 5], or a callable taking the kept proposals' sizes (in batch order) and returning that tensor."""
 
-    def __init__(self, model, num_points: int = 20000, max_iters: int = 100):
+    def __init__(self, model, num_points: int = 20000, max_iters: int = 100, sampler: str = "fps"):
         self.model, self.num_points, self.max_iters = model.eval(), int(num_points), int(max_iters)
+        self.sampler = _check_sampler(sampler)  # "grid": the opt-in octree-cell sampler (clouds take the seeds 0, 1, ...)
 
     def _empty(self, n: int, C: int, status: int, scale, dev) -> PartPrediction:
         i64, f32 = torch.int64, torch.float32
@@ -539,7 +608,7 @@ class PartPredictor:
 
     @torch.no_grad()
     def predict(self, clouds: Sequence[torch.Tensor], picks: Picks = None) -> List[PartPrediction]:
-        return self._predict_prepared(prepare_clouds(clouds, self.num_points), picks)
+        return self._predict_prepared(prepare_clouds(clouds, self.num_points, sampler=self.sampler), picks)
 
     def _predict_prepared(self, prep: PreparedClouds, picks: Picks = None) -> List[PartPrediction]:
         """everything behind the preparation, shared by ``predict`` (raw clouds) and ``predict_frames`` (RGB-D frames)"""
@@ -614,7 +683,8 @@ class PartPredictor:
         never a member), ``labels[s]`` [K_s] part classes.  A mask with fewer than ``min_points`` SAMPLED members is dropped (the
         reference's ``sum > 5``, structure/gapartnet.py:635).  Every kept mask is fitted with its OWN NPCS (a point shared by two
         masks carries two predictions); a box needs at least 5 points and a valid fit (the reference's ``<= 4: continue``)."""
-        return self._predict_masks_prepared(prepare_clouds(clouds, self.num_points), masks, labels, picks, min_points)
+        return self._predict_masks_prepared(prepare_clouds(clouds, self.num_points, sampler=self.sampler), masks, labels, picks,
+                                            min_points)
 
     def _predict_masks_prepared(self, prep: PreparedClouds, masks, labels, picks: Picks = None, min_points: int = 6) -> List[MaskPrediction]:
         """everything behind the preparation, shared by ``predict_with_masks`` and ``predict_frames_with_masks``"""
@@ -761,7 +831,7 @@ class PartPredictor:
         scale), the model's own (voxelisation, proposal stage), post-processing, box selection, ONE for the scenes of the proposals
         and boxes; ``K`` is host data."""
         depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
-        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip)
+        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip, sampler=self.sampler)
         return self._frame_predictions(self._predict_prepared(prep, picks), rgb, K, flip)
 
     @torch.no_grad()
@@ -799,7 +869,7 @@ class PartPredictor:
         ask = [v for v, lab in enumerate(labels) if lab is None]
         if ask:
             labels, votes = self._ground_labels(ask, labels, votes, masks, (H, W), V, features, grounder)
-        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip)
+        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip, sampler=self.sampler)
         mp = self._predict_masks_prepared(prep, flat, labels, picks, min_points)
         for p, vt in zip(mp, votes):
             p.label_votes = vt
@@ -953,7 +1023,7 @@ def _main_frames(ap, args, model, device) -> int:
             ap.error(f"{p}: the image must be [{d.shape[0]}, {d.shape[1]}, 3], got {c.shape}")
     names = [os.path.splitext(os.path.basename(p))[0] for p in args.depth]
     os.makedirs(args.out, exist_ok=True)
-    predictor = PartPredictor(model, num_points=args.num_points)
+    predictor = PartPredictor(model, num_points=args.num_points, sampler=args.sampler)
     preds: List[Optional[FramePrediction]] = [None] * n
     # (one batch per frame size and depth type)
     for key in sorted({(d.shape, d.dtype.str) for d in depth}):
@@ -1000,6 +1070,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--seed", type=int, default=0, help="frames: seed of the presample (frame i of the command line takes seed + i)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--num_points", type=int, default=20000)
+    ap.add_argument("--sampler", choices=SAMPLERS, default="fps",
+                    help="how a cloud or frame is cut to num_points: fps (what the checkpoints were trained on) or grid, the "
+                         "octree-cell sampler - far faster on large inputs, a coarser cover")
     ap.add_argument("--inference_dtype", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--panels", action="store_true")
     ap.add_argument("--no_flip", action="store_true", help="keep the y and z signs of .obj inputs")
@@ -1042,7 +1115,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     os.makedirs(args.out, exist_ok=True)
     # (one batch per column count: a batch shares its C)
     preds: List[Optional[PartPrediction]] = [None] * len(clouds)
-    predictor = PartPredictor(model, num_points=args.num_points)
+    predictor = PartPredictor(model, num_points=args.num_points, sampler=args.sampler)
     for C in sorted({int(c.shape[1]) for c in clouds}):
         ids = [i for i, c in enumerate(clouds) if c.shape[1] == C]
         for i, p in zip(ids, predictor.predict([clouds[i] for i in ids])):

@@ -910,6 +910,55 @@ int gpn_frame_select(const float* rows, const uint8_t* valid, const int32_t* val
                      size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * GS - an opt-in sampler for inference that is not sequential: octree cells instead of furthest point sampling.  It fills the slot
+ * of gpn_view_fps between gpn_cloud_pack / gpn_frame_select and gpn_cloud_finish; its cost is one sort and a few passes over the
+ * rows.  DECISION: opt-in only.  The checkpoints were trained on FPS-sampled clouds, so FPS stays the default of every entry point
+ * and the converter (section VP) is not touched: training data stays what the reference produces.  No host read between the
+ * launches; no float atomics; integer atomics only where order cannot matter (min / max by integer compare, histograms,
+ * counters); every output is bit-reproducible and a pure function of the cloud's rows and its seed - not of the other clouds of
+ * the call, of launch order or of the grid size.
+ * packed [S, n_bound, 4] f32, counts [S] i32 and status [S] i32 are what gpn_cloud_pack / gpn_frame_select write (S <= 65535,
+ * S * n_bound < 2^31); packed is NOT written (gpn_view_fps overwrites .w).  seeds [S] u32; hash_bits 1 .. 32 (callers pass 32; small
+ * values force hash ties in tests, as in section FR).  idx [S, m] i32 = packed row indices, read by gpn_cloud_finish as it reads
+ * FPS's; level [S] i32 = the octree level L* that was used, -1 where nothing was sampled.
+ * Per cloud with status GPN_CLOUD_OK and n = counts[s]: n < m sets GPN_CLOUD_FEW, leaves idx untouched, level = -1 (the rule of
+ * gpn_view_fps); n == m gives idx = 0 .. m-1, level = -1; a cloud whose status is not OK is skipped (level = -1); n > m is sampled
+ * (j = the packed index of a row, p its xyz):
+ *   1. lo_a, hi_a = the fp32 min and max per axis over the n rows; e = the largest of the three fp32 differences hi_a - lo_a.
+ *   2. e > 0 and finite: s = (float)(1024.0 / (double)e), q_a = (uint32)min((p_a - lo_a) * s, 1023.0f) - the subtraction and the
+ *      product one fp32 operation each, the cast truncating.  Otherwise (all points equal, an overflowing extent) every q_a = 0.
+ *      DECISION: min(x, 1023) is "x if x < 1023 else 1023": an extent so small that s overflows to +inf gives 0 * inf = NaN on
+ *      the rows at lo_a, which therefore land in cell 1023 with all the others of that axis.
+ *   3. code = the 30-bit Morton code, bit 3i + a of code = bit i of q_a (a = 0, 1, 2 for x, y, z).  The point's key is
+ *      (uint64)code << 32 | j; its level-L cell is code >> (30 - 3L), L = 0 .. 10.
+ *   4. C_L = the number of occupied level-L cells (C_0 = 1).  L* = the largest L with C_L <= m.
+ *   5. Stage A: every occupied level-L* cell contributes its point of smallest key.  r = m - C_L*.
+ *   6. Stage B (r > 0), with hq(v) = mix(mix(v + seed * 0x9E3779B9) ^ seed) >> (32 - hash_bits), the hash of section FR:
+ *      L* < 10: of the occupied level-(L*+1) cells that hold no stage-A point (C_{L*+1} - C_L* > r of them) the r with the smallest
+ *      (uint64)hq(cell) << 32 | cell, each contributing its point of smallest key.  L* == 10: of the points stage A did not take
+ *      the r with the smallest (uint64)hq(j) << 32 | j.
+ *   7. idx[s, :] = the m chosen packed indices in ASCENDING order; level[s] = L*.
+ *   Every point shares a level-L* cell (edge e / 2^L*) with a stage-A sample: the coverage radius is at most sqrt(3) e / 2^L*
+ *   plus the quantisation slack.  DECISION: 10 bits an axis and no more.  A cloud whose extent is dominated by a few far outliers
+ *   fills few cells per level, reaches L* == 10 with C_10 <= m and degrades into the hashed fill of that branch - a uniform
+ *   random subset of the points stage A left, no worse than the presample of section FR.
+ * How: the workgroups of a cloud share it in chunks of 1024 rows, as in section FR.  Bounds by integer atomicMin / atomicMax on
+ * the order-preserving integer image of the floats; ONE stable rocprim::radix_sort_pairs over the keys (cloud, dead, code) of all
+ * S * n_bound rows with the row index as payload - a cloud's live rows come out first in its own segment, ordered by (code, j);
+ * adjacent sorted codes give, per row, the first level at which it opens a new cell, and a 12-bin histogram of that gives all
+ * eleven C_L.  DECISION: the stage-A point of a cell is the first row of the cell in sorted order, and a level-(L*+1) cell holds
+ * no stage-A point exactly when its first row opens a cell at level L*+1 and not at L* - both read off the same per-row level.
+ * Stage B's r-th smallest hash is the radix select of gpn_frame_select (8 bits a pass, LDS histograms, threshold and tie count
+ * resolved on the device; ties admitted in ascending cell / row order).  The output is a flag per row, per-chunk counts and
+ * ballot-ordered stores, not a second sort.
+ * gpn_cloud_grid_sample_ws_bytes(S, n_bound): the workspace, 0 for S <= 0 or n_bound <= 0.  Errors (GPN_ERR_ARG, nothing
+ * launched): m < 1, hash_bits outside 1 .. 32, S > 65535, S * n_bound >= 2^31, a null pointer, a workspace smaller than that.
+ * ================================================================================================ */
+size_t gpn_cloud_grid_sample_ws_bytes(int S, int64_t n_bound);
+int gpn_cloud_grid_sample(const float* packed, int64_t n_bound, const int32_t* counts, int32_t* status, const uint32_t* seeds, int S,
+                          int m, int hash_bits, int32_t* idx, int32_t* level, void* ws, size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * RD - articulated assets -> training views (the reference's dataset/render_tools/render.py without SAPIEN): z-depth, the winning
  * triangle, link labels, the NPCS map and a flat-shaded RGB image for a batch of V views of one size H x W (H, W <= 16384, V <=
  * 65535).  Views may show different assets.  No host read between the launches; no float atomics; every pixel is stored once, so
