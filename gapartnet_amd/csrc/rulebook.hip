@@ -157,6 +157,9 @@ __global__ __launch_bounds__(1024) void lists_block_scan_kernel(int32_t* __restr
   if (n_dev) {
     const int64_t n_tiles = (gpn::live_rows(n_dev, n_dst_bound) + GPN_TILE_ROWS - 1) / GPN_TILE_ROWS;
     n = ((int64_t)K * n_tiles + kListTilesPerWg - 1) / kListTilesPerWg;
+    // an empty table has no tile whose compaction would write the end marker of the tap before it: all K of them here (the
+    // host-counted form zeroes the offsets of an empty table)
+    if (n_tiles == 0 && threadIdx.x < K) total[threadIdx.x] = 0;
     total += (int64_t)(K - 1) * (n_tiles + 1) + n_tiles;
   }
   const int tid = threadIdx.x;
@@ -589,6 +592,7 @@ static int rulebook_subm3_impl(const int32_t* indices, int64_t N, const gpn::Dev
   const int64_t n_tiles = gpn::cdiv(N, GPN_TILE_ROWS);
   if (N == 0) {
     GPN_CHECK_HIP(hipMemsetAsync(tile_off, 0, sizeof(int32_t) * 27 * (n_tiles + 1), stream));
+    if (nbr) GPN_CHECK_HIP(hipMemsetAsync(nbr, 0xff, sizeof(int32_t), stream));  // the -1 sentinel behind the (empty) table
     if (num_pairs) GPN_CHECK_HIP(hipMemsetAsync(num_pairs, 0, sizeof(int64_t), stream));
     return GPN_OK;
   }
@@ -931,6 +935,10 @@ static int rulebook_down_lists_impl(const int32_t* fine_to_coarse, const int32_t
   if (N == 0 || n_out == 0) {
     GPN_CHECK_HIP(hipMemsetAsync(fwd_tile_off, 0, sizeof(int32_t) * 8 * (nt_f + 1), stream));
     GPN_CHECK_HIP(hipMemsetAsync(bwd_tile_off, 0, sizeof(int32_t) * 8 * (nt_b + 1), stream));
+    // no pair, but the tables are read by the fused conv kernels: no neighbour anywhere (-1), sentinel included.  Fine rows without
+    // a coarse row happen (every row in a batch entry >= batch_size, or in the plane an odd extent drops).
+    if (fwd_nbr) GPN_CHECK_HIP(hipMemsetAsync(fwd_nbr, 0xff, sizeof(int32_t) * (size_t)(8 * n_out + 1), stream));
+    if (bwd_nbr) GPN_CHECK_HIP(hipMemsetAsync(bwd_nbr, 0xff, sizeof(int32_t) * (size_t)(8 * N + 1), stream));
     if (num_pairs) GPN_CHECK_HIP(hipMemsetAsync(num_pairs, 0, sizeof(int64_t), stream));
     return GPN_OK;
   }

@@ -182,7 +182,13 @@ int gpn_rulebook_tile_order(const int32_t* nbr, int K, int64_t n, int block_rows
  * (-1 = dropped), tap [N] i32 = (x&1)*4+(y&1)*2+(z&1), num_out [1] i64.
  * The two pair-list views (dst = coarse for the down conv / dgrad of the inverse conv;
  * dst = fine for the inverse conv / dgrad of the down conv) are then built with
- * gpn_rulebook_down_lists once num_out is known on the host. */
+ * gpn_rulebook_down_lists once num_out is known on the host.
+ * Two forms, chosen by the workspace passed in: when an occupancy bitmap of the coarse grid (8 bytes per 64 cells of
+ * batch_size * floor(D/2)^3, + 4 bytes per word of prefixes, + 4 bytes per 1024 words) fits ws_bytes, the coarse rows are
+ * ranked by popcount prefixes over it (no sort); otherwise the rows' coarse keys are radix-sorted, which needs only the
+ * gpn_rulebook_down_ws_bytes(N) bytes.  Both forms give identical outputs (tests/test_gpu_rulebooks.py), so a larger
+ * workspace only makes the call faster.  Rows with a batch entry outside [0, batch_size) or a negative coordinate are dropped.
+ * gpn_rulebook_down_lists with n_out == 0 (every row dropped) writes all-zero offsets and tables of -1. */
 size_t gpn_rulebook_down_ws_bytes(int64_t N);
 int gpn_rulebook_down(const int32_t* indices, int64_t N, int64_t batch_size,
                       const int32_t* spatial_shape_host, int32_t* out_indices, int32_t* fine_to_coarse, int32_t* tap, int64_t* num_out,
