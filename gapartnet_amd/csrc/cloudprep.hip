@@ -234,19 +234,7 @@ __global__ __launch_bounds__(kThreads) void cn_build_kernel(const float* __restr
   __syncthreads();
   for (int j = tid; j < ms; j += kThreads) atomicAdd(&cells[cell_of(sample(j))], 1);  // (integer counts: order-free)
   __syncthreads();
-  // exclusive scan in place: thread t owns cells [t * chunk, (t + 1) * chunk)
-  const int chunk = (ncells + kThreads - 1) / kThreads;
-  const int c0 = min(tid * chunk, ncells), c1 = min(c0 + chunk, ncells);
-  int sum = 0;
-  for (int c = c0; c < c1; ++c) sum += cells[c];
-  int total;
-  int run = block_scan<kWaves>(sum, wsum, &total) - sum;
-  for (int c = c0; c < c1; ++c) {
-    const int v = cells[c];
-    cells[c] = run;
-    run += v;
-  }
-  __syncthreads();
+  block_scan_runs<kWaves>(cells, ncells, wsum);  // counts -> first slots, in place
   // stable scatter, a tile of kThreads samples at a time in sample order: a sample's slot is its cell's cursor plus the number
   // of earlier samples of the tile in the same cell; the cell's last sample of the tile moves the cursor
   for (int t0 = 0; t0 < ms; t0 += kThreads) {

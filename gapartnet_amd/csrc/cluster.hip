@@ -3,6 +3,7 @@
 // Replaces epic_ops.{ball_query,ccl,reduce,iou,nms} (network/grouping_utils.py:59-70,119-137,244;
 // network/model.py:360-362,373-378).
 #include "gpn_common.h"
+#include "wg_scan.h"
 
 namespace {
 
@@ -188,28 +189,10 @@ __global__ void ccl_flatten_kernel(int32_t* parent, int64_t Q, int32_t* __restri
   if (is_root) is_root[i] = (r == (int32_t)i) ? 1 : 0;
 }
 
-// compaction: rank[i] = number of roots with index < i  (single-workgroup blocked scan; Q is modest)
-__global__ void ccl_rank_kernel(const int32_t* __restrict__ is_root, int64_t Q, int32_t* __restrict__ rank) {
-  __shared__ int32_t sums[1024];
-  __shared__ int32_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < Q; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int32_t v = i < Q ? is_root[i] : 0;
-    sums[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      int32_t t = threadIdx.x >= off ? sums[threadIdx.x - off] : 0;
-      __syncthreads();
-      sums[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < Q) rank[i] = carry + sums[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sums[1023];
-    __syncthreads();
-  }
+// compaction: rank[i] = number of roots with index < i  (one workgroup of 1024; Q is modest)
+__global__ __launch_bounds__(1024) void ccl_rank_kernel(const int32_t* __restrict__ is_root, int64_t Q, int32_t* __restrict__ rank) {
+  __shared__ int32_t wsum[16];
+  gpn::block_scan_tiled<16>(Q, [&](int64_t i) { return is_root[i]; }, rank, wsum);
 }
 __global__ void ccl_relabel_kernel(int32_t* __restrict__ labels, const int32_t* __restrict__ rank, int64_t Q) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

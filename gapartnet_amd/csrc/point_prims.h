@@ -1,8 +1,9 @@
 // point_prims.h — the building blocks the point front ends share (pointnet2.hip, viewprep.hip, cloudprep.hip, frameprep.hip,
-// gridsample.hip): the no-fma distance, workgroup integer scan / sum, the seeded hash with the resolve step of its radix select,
+// gridsample.hip): the no-fma distance, the seeded hash with the resolve step of its radix select,
 // ballot-ordered ranks, the furthest-point-sampling candidate with its three reduction steps, and the ball normalisation.  Every one of them is pinned bit for bit by the oracle; this is their only definition.
 #pragma once
 #include "gpn_common.h"
+#include "wg_scan.h"  // block_sum / block_scan: the workgroup integer sum and scan
 
 namespace gpn {
 
@@ -23,45 +24,6 @@ __device__ __forceinline__ double wave_max(double a) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) a = fmax(a, __shfl_xor(a, off, 64));
   return a;
-}
-
-// ---- one int per thread over a workgroup of kWaves waves; wsum: kWaves ints of LDS, free again when the call returns ----------
-// sum (every thread gets it)
-template <int kWaves>
-__device__ __forceinline__ int block_sum(int c, int* wsum) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  int tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) tot += wsum[w];
-  __syncthreads();  // wsum is rewritten by the next call
-  return tot;
-}
-
-// inclusive scan: -> (this thread's inclusive sum, the workgroup's total)
-template <int kWaves>
-__device__ __forceinline__ int block_scan(int c, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int s = wsum[w];
-    before += w < wave ? s : 0;
-    tot += s;
-  }
-  __syncthreads();  // wsum is rewritten by the next call
-  *total = tot;
-  return before + incl;
 }
 
 // ---- seeded radix select (include/gpn.h sections FR and GS): the k smallest 64-bit keys (hash << 32) | item of a set -------------

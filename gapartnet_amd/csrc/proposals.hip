@@ -21,6 +21,7 @@
 //  * re-voxelisation reuses kernel V (gpn_voxelize_ex) on the padded point list: rows past M fall outside the last
 //    segment and are dropped by the kernel's own range test.
 #include "gpn_common.h"  // first: pulls <cstring> ahead of the HIP/rocPRIM headers
+#include "wg_scan.h"
 
 #include <mutex>
 #include <rocprim/rocprim.hpp>
@@ -366,83 +367,30 @@ __global__ __launch_bounds__(1024) void revox_scan_kernel(const int32_t* __restr
                                                           const int32_t* __restrict__ n_vox, const int32_t* __restrict__ n_out,
                                                           int32_t* __restrict__ vox_base, int32_t* __restrict__ kept_base,
                                                           int32_t* __restrict__ out_base, int32_t* __restrict__ vstart) {
-  __shared__ int part[3][1024];
-  __shared__ int carry[3];
+  __shared__ int wsum[16];
   const int t = threadIdx.x;
   const int64_t P = counts[kP];
-  if (t < 3) carry[t] = 0;
-  __syncthreads();
+  int carry[3] = {0, 0, 0};
   for (int64_t p0 = 0; p0 < P; p0 += 1024) {
     const int64_t p = p0 + t;
-    int v[3] = {0, 0, 0};
+    int v[3] = {0, 0, 0}, first[3];
     if (p < P) {
       const int size = proposal_offsets[p + 1] - proposal_offsets[p];
       v[0] = n_vox[p], v[2] = n_out[p], v[1] = size - v[2];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) part[k][t] = v[k];
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {  // inclusive Hillis-Steele over the chunk
-      int add[3] = {0, 0, 0};
-      if (t >= off) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) add[k] = part[k][t - off];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 3; ++k) part[k][t] += add[k];
-      __syncthreads();
+    for (int k = 0; k < 3; ++k) {
+      int total;
+      first[k] = carry[k] + gpn::block_scan<16>(v[k], wsum, &total) - v[k];
+      carry[k] += total;
     }
-    if (p < P) {
-      vox_base[p] = carry[0] + part[0][t] - v[0];
-      kept_base[p] = carry[1] + part[1][t] - v[1];
-      out_base[p] = carry[2] + part[2][t] - v[2];
-    }
-    __syncthreads();
-    if (t < 3) carry[t] += part[t][1023];
-    __syncthreads();
+    if (p < P) vox_base[p] = first[0], kept_base[p] = first[1], out_base[p] = first[2];
   }
   if (t == 0) {
     counts[kV] = carry[0];
     vstart[carry[0]] = carry[1];
     kept_base[P] = carry[1];  // (total of kept points, read by the place kernel)
   }
-}
-
-// exclusive prefix of one value per thread over the workgroup's 256 threads (+ the total): wave shuffles, then the 4 wave totals
-__device__ __forceinline__ int revox_thread_scan(int v, int* wave_tot /* [4] */, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  int before = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) before += w < wave ? wave_tot[w] : 0;
-  total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  __syncthreads();
-  return before + incl - v;
-}
-// in-place exclusive sum of a[0 .. n) in LDS by the workgroup (a contiguous run per thread); returns the total
-__device__ __forceinline__ int revox_block_scan(int* a, int n, int* wave_tot) {
-  const int t = threadIdx.x;
-  const int run_len = (n + kThreads - 1) / kThreads;
-  const int b = min(t * run_len, n), e = min(b + run_len, n);
-  int s = 0;
-  for (int i = b; i < e; ++i) s += a[i];
-  int total;
-  int run = revox_thread_scan(s, wave_tot, total);
-  for (int i = b; i < e; ++i) {
-    const int c = a[i];
-    a[i] = run;
-    run += c;
-  }
-  __syncthreads();
-  return total;
 }
 
 __global__ __launch_bounds__(kThreads) void revox_place_kernel(const float* __restrict__ scaled,
@@ -477,7 +425,7 @@ __global__ __launch_bounds__(kThreads) void revox_place_kernel(const float* __re
     __syncthreads();
     for (int w = t; w < words; w += kThreads) wprefix[w] = __builtin_popcount(bm[w]);
     __syncthreads();
-    const int n_vox = revox_block_scan(wprefix, words, wave_tot);
+    const int n_vox = gpn::block_scan_runs<kThreads / 64>(wprefix, words, wave_tot);
     for (int v = t; v <= n_vox; v += kThreads) cur[v] = 0;
     __syncthreads();
     for (int64_t m = b + t; m < e; m += kThreads) {
@@ -485,7 +433,7 @@ __global__ __launch_bounds__(kThreads) void revox_place_kernel(const float* __re
       atomicAdd(&cur[cell >= 0 ? local_voxel(cell) : n_vox], 1);
     }
     __syncthreads();
-    revox_block_scan(cur, n_vox, wave_tot);  // (cur[n_vox], the dropped points' count, is not part of the sum)
+    gpn::block_scan_runs<kThreads / 64>(cur, n_vox, wave_tot);  // (cur[n_vox], the dropped points' count, is not part of the sum)
     if (t == 0) cur[n_vox] = 0;
     const int vb = vox_base[p], kb = kept_base[p], ob = kept_total + out_base[p];
     for (int w = t; w < words; w += kThreads) {  // the proposal's voxels: first position, coordinates
@@ -978,47 +926,34 @@ __global__ __launch_bounds__(1024) void mp_scan_kernel(const int32_t* __restrict
                                                        int64_t* __restrict__ sizes, int32_t* __restrict__ proposal_offsets,
                                                        int64_t* __restrict__ proposal_mask, int64_t* __restrict__ seg64,
                                                        int64_t* __restrict__ counts) {
-  __shared__ long long part[3][1024];
-  __shared__ long long carry[3];
+  __shared__ int wsum[16];
+  __shared__ long long wsum64[16];
   const int t = threadIdx.x;
-  if (t < 3) carry[t] = 0;
-  __syncthreads();
+  int kept = 0, n_bad = 0;  // masks before this tile: kept, with an unknown label (counts of masks: 32 bits)
+  long long members = 0;    // members of the kept masks before this tile
   for (int64_t k0 = 0; k0 < K; k0 += 1024) {
     const int64_t k = k0 + t;
-    long long v[3] = {0, 0, 0};
-    if (k < K) v[0] = keep[k], v[1] = keep[k] ? size[k] : 0, v[2] = bad[k];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) part[q][t] = v[q];
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {  // inclusive Hillis-Steele over the chunk
-      long long add[3] = {0, 0, 0};
-      if (t >= off) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) add[q] = part[q][t - off];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < 3; ++q) part[q][t] += add[q];
-      __syncthreads();
-    }
+    const int kp = k < K ? keep[k] : 0, bd = k < K ? bad[k] : 0;
+    const long long sz = kp ? size[k] : 0;
+    int tile_kept;
+    long long tile_members;
+    const int p = kept + gpn::block_scan<16>(kp, wsum, &tile_kept) - kp;
+    const long long first = members + gpn::block_scan<16>(sz, wsum64, &tile_members) - sz;
     if (k < K) {
-      const long long p = carry[0] + part[0][t] - v[0], first = carry[1] + part[1][t] - v[1];
-      pid[k] = (int32_t)p;
-      if (v[0] && first + v[1] <= M_cap) {
-        sizes[p] = v[1];
+      pid[k] = p;
+      if (kp && first + sz <= M_cap) {
+        sizes[p] = sz;
         proposal_offsets[p] = (int32_t)first;
         proposal_mask[p] = k;
         seg64[p] = first;
       }
     }
-    __syncthreads();
-    if (t < 3) carry[t] += part[t][1023];
-    __syncthreads();
+    kept += tile_kept, members += tile_members, n_bad += gpn::block_sum<16>(bd, wsum);
   }
-  const bool over = carry[1] > M_cap;
-  const int64_t P = over ? 0 : carry[0], M = over ? 0 : carry[1];
+  const bool over = members > M_cap;
+  const int64_t P = over ? 0 : kept, M = over ? 0 : members;
   if (t == 0) {
-    counts[kP] = P, counts[kM] = M, counts[kBadLabel] = carry[2], counts[kOverflow] = over ? carry[1] : 0;
+    counts[kP] = P, counts[kM] = M, counts[kBadLabel] = n_bad, counts[kOverflow] = over ? members : 0;
   }
   for (int64_t p = P + t; p <= K; p += 1024) proposal_offsets[p] = (int32_t)M, seg64[p] = M;  // closing offset, empty tail segments
 }

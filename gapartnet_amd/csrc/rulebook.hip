@@ -5,12 +5,12 @@
 // Design (MI355X): coordinates -> row lookups go through an open-addressing hash table in HBM/L2
 // (64-bit linear keys, linear probing, one atomicCAS per insert); every other step is a coalesced
 // streaming pass over a tap-major [K][n_dst] table: lookup -> per-tile ballot counts -> a small scan of
-// the workgroup sums -> ballot-rank compaction into pair lists ordered by (tap, dst) (round 3; a
-// rocPRIM exclusive scan over the whole table before).  The counts double as the per-tile offset table
+// the workgroup sums -> ballot-rank compaction into pair lists ordered by (tap, dst).  The counts double as the per-tile offset table
 // the weight-gradient kernel walks, so no sort is ever needed for SubM rulebooks.  Stride-2 levels:
 // occupancy bitmap + popcount prefix (no sort either); the tile order of the large levels: masks by a
 // whole-chip launch, each 16384-row block sorted in one workgroup's LDS (rocPRIM block radix sort).
 #include "gpn_common.h"  // first: pulls <cstring> ahead of the HIP/rocPRIM headers
+#include "wg_scan.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -30,6 +30,35 @@ __device__ __forceinline__ uint64_t lin_key(int b, int x, int y, int z, int s0, 
   return (((uint64_t)b * (uint64_t)s0 + (uint64_t)x) * (uint64_t)s1 + (uint64_t)y) * (uint64_t)s2 + (uint64_t)z;
 }
 
+// slots of a table for N keys: a power of two, at most half full
+uint64_t hash_capacity(int64_t N) {
+  uint64_t cap = 1024;
+  while (cap < 2 * (uint64_t)(N > 0 ? N : 1)) cap <<= 1;
+  return cap;
+}
+
+// claim `key` in an open-addressing table (linear probing): an empty slot taken by atomicCAS, or the slot that holds the key
+// already.  -> the slot; *is_new: this call put the key there
+__device__ __forceinline__ uint64_t hash_claim(uint64_t* __restrict__ hkeys, uint64_t mask, uint64_t key, bool* is_new) {
+  uint64_t slot = mix64(key) & mask;
+  while (true) {
+    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(hkeys + slot), (unsigned long long)kEmpty,
+                                              (unsigned long long)key);
+    if (prev == kEmpty || prev == key) {
+      *is_new = prev == kEmpty;
+      return slot;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+// device-counted rows (n_dev != nullptr): the live count and its 32-row tiles take the place of the bounds
+__device__ __forceinline__ void live_tiles(const int64_t* n_dev, int64_t& n, int64_t& n_tiles) {
+  if (!n_dev) return;
+  n = gpn::live_rows(n_dev, n);
+  n_tiles = (n + GPN_TILE_ROWS - 1) / GPN_TILE_ROWS;
+}
+
 // (every builder kernel below takes the row count either as an argument or - n_dev != nullptr, gpn::DevRows - from a device
 // counter, and walks its elements with a grid stride: one round when the grid was sized from the count)
 __global__ void hash_insert_kernel(const int32_t* __restrict__ indices, int64_t N, int s0, int s1, int s2,
@@ -39,17 +68,8 @@ __global__ void hash_insert_kernel(const int32_t* __restrict__ indices, int64_t 
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
     const int4 c = reinterpret_cast<const int4*>(indices)[i];
     const uint64_t key = lin_key(c.x, c.y, c.z, c.w, s0, s1, s2);
-    uint64_t slot = mix64(key) & mask;
-    while (true) {
-      unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(hkeys + slot),
-                                          (unsigned long long)kEmpty, (unsigned long long)key);
-      if (prev == kEmpty || prev == key) {
-        // duplicates: the highest row id wins deterministically
-        atomicMax(hvals + slot, (int32_t)i);
-        break;
-      }
-      slot = (slot + 1) & mask;
-    }
+    bool is_new;
+    atomicMax(hvals + hash_claim(hkeys, mask, key, &is_new), (int32_t)i);  // duplicates: the highest row id wins deterministically
   }
 }
 
@@ -86,14 +106,9 @@ __global__ void subm3_lookup_kernel(const int32_t* __restrict__ indices, int64_t
   }
 }
 
-struct ValidFlag {
-  __device__ __host__ int32_t operator()(int32_t v) const { return v >= 0 ? 1 : 0; }
-};
-
 // ---- pair lists from the tap-major table: wave ballots, no device-wide scan over the table (round 3) ------------------------
 // pair_src / pair_dst = the valid entries of table [K, n_dst] in (tap, row) order; tile_off[k][t] = position of the first pair
-// of tap k at or behind row 32 t; tile_off[k][n_tiles] = end of tap k.  Until round 3: a rocPRIM exclusive scan over all
-// K n_dst + 1 entries (4 M at level 0: a 16 MB position array written and read back) + a compaction launch.  Now:
+// of tap k at or behind row 32 t; tile_off[k][n_tiles] = end of tap k.
 //   A  lists_count_kernel    a half-wave per (tap, 32-row tile): ballot + popcount = the tile's pair count; a workgroup's eight
 //                            counts and their sum go to a scratch array
 //   B  lists_block_scan_kernel   ONE workgroup: exclusive scan of the workgroup sums (15 k of them at level 0), total
@@ -118,10 +133,7 @@ __global__ __launch_bounds__(256) void lists_count_kernel(const int32_t* __restr
                                                           int32_t* __restrict__ counts, int32_t* __restrict__ wg_sum,
                                                           const int64_t* __restrict__ n_dev) {
   __shared__ int32_t c[kListTilesPerWg];
-  if (n_dev) {
-    n_dst = gpn::live_rows(n_dev, n_dst);
-    n_tiles = (n_dst + GPN_TILE_ROWS - 1) / GPN_TILE_ROWS;
-  }
+  live_tiles(n_dev, n_dst, n_tiles);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
   const int64_t n_wg = ((int64_t)K * n_tiles + kListTilesPerWg - 1) / kListTilesPerWg;
   for (int64_t b = blockIdx.x; b < n_wg; b += gridDim.x) {
@@ -153,37 +165,20 @@ __global__ __launch_bounds__(256) void lists_count_kernel(const int32_t* __restr
 __global__ __launch_bounds__(1024) void lists_block_scan_kernel(int32_t* __restrict__ wg_sum, int64_t n, int32_t* __restrict__ total,
                                                                 int64_t* __restrict__ num_pairs, int K, int64_t n_dst_bound,
                                                                 const int64_t* __restrict__ n_dev) {
-  __shared__ int32_t part[1024];
+  __shared__ int32_t wsum[16];
   if (n_dev) {
-    const int64_t n_tiles = (gpn::live_rows(n_dev, n_dst_bound) + GPN_TILE_ROWS - 1) / GPN_TILE_ROWS;
+    int64_t n_tiles = 0;
+    live_tiles(n_dev, n_dst_bound, n_tiles);
     n = ((int64_t)K * n_tiles + kListTilesPerWg - 1) / kListTilesPerWg;
     // an empty table has no tile whose compaction would write the end marker of the tap before it: all K of them here (the
     // host-counted form zeroes the offsets of an empty table)
     if (n_tiles == 0 && threadIdx.x < K) total[threadIdx.x] = 0;
     total += (int64_t)(K - 1) * (n_tiles + 1) + n_tiles;
   }
-  const int tid = threadIdx.x;
-  const int64_t chunk = (n + 1023) / 1024;
-  const int64_t b = tid * chunk, e = b + chunk < n ? b + chunk : n;
-  int32_t sum = 0;
-  for (int64_t i = b; i < e; ++i) sum += wg_sum[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {  // inclusive scan of the 1024 chunk sums
-    const int32_t add = tid >= off ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  int32_t run = tid > 0 ? part[tid - 1] : 0;
-  for (int64_t i = b; i < e; ++i) {
-    const int32_t v = wg_sum[i];
-    wg_sum[i] = run;
-    run += v;
-  }
-  if (tid == 1023) {
-    *total = part[1023];
-    if (num_pairs) *num_pairs = part[1023];
+  const int32_t sum = gpn::block_scan_tiled<16>(n, [&](int64_t i) { return wg_sum[i]; }, wg_sum, wsum);
+  if (threadIdx.x == 0) {
+    *total = sum;
+    if (num_pairs) *num_pairs = sum;
   }
 }
 
@@ -191,10 +186,7 @@ __global__ __launch_bounds__(256) void lists_compact_kernel(const int32_t* __res
                                                             const int32_t* __restrict__ counts, const int32_t* __restrict__ wg_off,
                                                             int32_t* __restrict__ pair_src, int32_t* __restrict__ pair_dst,
                                                             int32_t* __restrict__ tile_off, const int64_t* __restrict__ n_dev) {
-  if (n_dev) {
-    n_dst = gpn::live_rows(n_dev, n_dst);
-    n_tiles = (n_dst + GPN_TILE_ROWS - 1) / GPN_TILE_ROWS;
-  }
+  live_tiles(n_dev, n_dst, n_tiles);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
   const int slot = wave * 2 + half;
   const int64_t F = (int64_t)K * n_tiles;
@@ -225,10 +217,6 @@ __global__ __launch_bounds__(256) void lists_compact_kernel(const int32_t* __res
   }
 }
 
-__global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) p[t] = v;
-}
 // a[0 .. na) = b[0 .. nb) = v; with device counters: na = ka * *na_dev + 1, nb = kb * *nb_dev + 1 (tables of live size)
 __global__ void fill_two_i32_kernel(int32_t* a, int64_t na, int32_t* b, int64_t nb, int32_t v, int ka, const int64_t* na_dev,
                                     int kb, const int64_t* nb_dev) {
@@ -240,21 +228,11 @@ __global__ void fill_two_i32_kernel(int32_t* a, int64_t na, int32_t* b, int64_t 
   }
 }
 
-size_t scan_temp_bytes(int64_t n) {
-  size_t bytes = 0;
-  auto in = rocprim::make_transform_iterator((const int32_t*)nullptr, ValidFlag());
-  rocprim::exclusive_scan(nullptr, bytes, in, (int32_t*)nullptr, 0, (size_t)(n > 0 ? n : 1),
-                          rocprim::plus<int32_t>(), (hipStream_t) nullptr);
-  return bytes;
-}
-
-// table: [K*n_dst + 1] with table[K*n_dst] == -1.  pos: [K*n_dst + 1].
+// table: [K*n_dst + 1] with table[K*n_dst] == -1.
 // scratch (`pos`): K n_tiles tile counts + one sum per workgroup of 8 tiles; callers size it K n_dst + 64 ints
 int lists_from_table(const int32_t* table, int32_t* pos, int K, int64_t n_dst, int32_t* pair_src,
-                     int32_t* pair_dst, int32_t* tile_off, int64_t* num_pairs, void* prim_tmp,
-                     size_t prim_bytes, hipStream_t stream, const gpn::DevRows& rows = gpn::DevRows()) {
-  (void)prim_tmp;
-  (void)prim_bytes;
+                     int32_t* pair_dst, int32_t* tile_off, int64_t* num_pairs, hipStream_t stream,
+                     const gpn::DevRows& rows) {
   const int64_t n_tiles = gpn::cdiv(n_dst, GPN_TILE_ROWS);
   const int64_t F = (int64_t)K * n_tiles;
   const int64_t n_wg = gpn::cdiv(F, kListTilesPerWg);
@@ -273,23 +251,33 @@ int lists_from_table(const int32_t* table, int32_t* pos, int K, int64_t n_dst, i
   return GPN_OK;
 }
 
-uint64_t hash_capacity(int64_t N) {
-  uint64_t cap = 1024;
-  while (cap < (uint64_t)(2 * N)) cap <<= 1;
-  return cap;
+// ------------------------------------------------------------------------------------------ down
+// The stride-2 rule for one fine row (batch, x, y, z): its coarse cell is (batch, x >> 1, y >> 1, z >> 1) - `ok` when the batch
+// entry is below nb and the cell inside the coarse shape (o0, o1, o2), `key` its linear key - and its tap the three parity bits.
+struct DownCell {
+  int4 c;  // the coarse row of indices
+  int tap;
+  bool ok;
+  uint64_t key;
+};
+__device__ __forceinline__ DownCell down_cell(const int32_t* __restrict__ indices, int64_t i, int nb, int o0, int o1, int o2) {
+  const int4 f = reinterpret_cast<const int4*>(indices)[i];
+  DownCell d;
+  d.c = make_int4(f.x, f.y >> 1, f.z >> 1, f.w >> 1);
+  d.tap = (f.y & 1) * 4 + (f.z & 1) * 2 + (f.w & 1);
+  d.ok = f.x >= 0 && f.x < nb && f.y >= 0 && f.z >= 0 && f.w >= 0 && d.c.y < o0 && d.c.z < o1 && d.c.w < o2;
+  d.key = lin_key(d.c.x, d.c.y, d.c.z, d.c.w, o0, o1, o2);  // (meaningless unless ok)
+  return d;
 }
 
-// ------------------------------------------------------------------------------------------ down
 __global__ void down_keys_kernel(const int32_t* __restrict__ indices, int64_t N, int nb, int o0, int o1, int o2,
                                  uint64_t invalid_key, uint64_t* __restrict__ keys,
                                  uint32_t* __restrict__ vals, int32_t* __restrict__ tap) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const int4 c = reinterpret_cast<const int4*>(indices)[i];
-  const int x = c.y >> 1, y = c.z >> 1, z = c.w >> 1;
-  tap[i] = (c.y & 1) * 4 + (c.z & 1) * 2 + (c.w & 1);
-  const bool ok = c.x >= 0 && c.x < nb && c.y >= 0 && c.z >= 0 && c.w >= 0 && x < o0 && y < o1 && z < o2;
-  keys[i] = ok ? lin_key(c.x, x, y, z, o0, o1, o2) : invalid_key;
+  const DownCell d = down_cell(indices, i, nb, o0, o1, o2);
+  tap[i] = d.tap;
+  keys[i] = d.ok ? d.key : invalid_key;
   vals[i] = (uint32_t)i;
 }
 
@@ -350,13 +338,9 @@ __global__ void down_mark_kernel(const int32_t* __restrict__ indices, int64_t N,
                                  const int64_t* __restrict__ n_dev) {
   N = gpn::live_rows(n_dev, N);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-    const int4 c = reinterpret_cast<const int4*>(indices)[i];
-    const int x = c.y >> 1, y = c.z >> 1, z = c.w >> 1;
-    tap[i] = (c.y & 1) * 4 + (c.z & 1) * 2 + (c.w & 1);
-    const bool ok = c.x >= 0 && c.x < nb && c.y >= 0 && c.z >= 0 && c.w >= 0 && x < o0 && y < o1 && z < o2;
-    if (!ok) continue;
-    const uint64_t key = lin_key(c.x, x, y, z, o0, o1, o2);
-    atomicOr(bitmap + (key >> 6), 1ull << (key & 63));
+    const DownCell d = down_cell(indices, i, nb, o0, o1, o2);
+    tap[i] = d.tap;
+    if (d.ok) atomicOr(bitmap + (d.key >> 6), 1ull << (d.key & 63));
   }
 }
 
@@ -377,66 +361,34 @@ __global__ void bitmap_clear_kernel(unsigned long long* __restrict__ bitmap, int
 __global__ __launch_bounds__(256) void bitmap_scan_blocks_kernel(const unsigned long long* __restrict__ bitmap, int64_t n_words,
                                                                  int32_t* __restrict__ prefix, int32_t* __restrict__ block_sum,
                                                                  int64_t cells_per_entry, const int64_t* __restrict__ batch_dev) {
-  __shared__ int32_t wave_tot[4];
+  __shared__ int32_t wsum[4];
   n_words = live_words(n_words, cells_per_entry, batch_dev);
   const int64_t n_blocks = (n_words + kScanBlock - 1) / kScanBlock;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-    const int64_t base = blk * kScanBlock + t * 4;
+    const int64_t base = blk * kScanBlock + threadIdx.x * 4;
     int32_t c[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) c[q] = base + q < n_words ? __popcll(bitmap[base + q]) : 0;
     const int32_t mine = c[0] + c[1] + c[2] + c[3];
-    int32_t incl = mine;  // inclusive scan over the wave (ballot-free shuffle tree, fixed order)
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int32_t v = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int32_t wbase = 0;
-    for (int w = 0; w < wave; ++w) wbase += wave_tot[w];
-    int32_t run = wbase + incl - mine;
+    int32_t total;
+    int32_t run = gpn::block_scan<4>(mine, wsum, &total) - mine;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if (base + q < n_words) prefix[base + q] = run;
       run += c[q];
     }
-    if (t == 255) block_sum[blk] = wbase + incl;
-    __syncthreads();  // (wave_tot is rewritten by the next round)
+    if (threadIdx.x == 0) block_sum[blk] = total;
   }
 }
 
-// exclusive scan of the block totals by one workgroup (<= 256 K blocks); total -> num_out
+// exclusive scan of the block totals by one workgroup; total -> num_out
 __global__ __launch_bounds__(1024) void bitmap_scan_totals_kernel(int32_t* __restrict__ block_sum, int64_t n_blocks,
                                                                   int64_t* __restrict__ num_out, int64_t n_words,
                                                                   int64_t cells_per_entry, const int64_t* __restrict__ batch_dev) {
-  __shared__ int32_t part[1024];
+  __shared__ int32_t wsum[16];
   if (batch_dev) n_blocks = (live_words(n_words, cells_per_entry, batch_dev) + kScanBlock - 1) / kScanBlock;
-  const int t = threadIdx.x;
-  const int64_t per = (n_blocks + 1023) / 1024;
-  const int64_t b = t * per, e = b + per < n_blocks ? b + per : n_blocks;
-  int32_t s = 0;
-  for (int64_t i = b; i < e; ++i) s += block_sum[i];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int32_t run = 0;
-    for (int i = 0; i < 1024; ++i) {
-      const int32_t v = part[i];
-      part[i] = run;
-      run += v;
-    }
-    num_out[0] = run;
-  }
-  __syncthreads();
-  int32_t run = part[t];
-  for (int64_t i = b; i < e; ++i) {
-    const int32_t v = block_sum[i];
-    block_sum[i] = run;
-    run += v;
-  }
+  const int32_t total = gpn::block_scan_tiled<16>(n_blocks, [&](int64_t b) { return block_sum[b]; }, block_sum, wsum);
+  if (threadIdx.x == 0) num_out[0] = total;
 }
 
 __global__ void down_rank_kernel(const int32_t* __restrict__ indices, int64_t N, int nb, int o0, int o1, int o2,
@@ -445,18 +397,15 @@ __global__ void down_rank_kernel(const int32_t* __restrict__ indices, int64_t N,
                                  int32_t* __restrict__ fine_to_coarse, const int64_t* __restrict__ n_dev) {
   N = gpn::live_rows(n_dev, N);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-    const int4 c = reinterpret_cast<const int4*>(indices)[i];
-    const int x = c.y >> 1, y = c.z >> 1, z = c.w >> 1;
-    const bool ok = c.x >= 0 && c.x < nb && c.y >= 0 && c.z >= 0 && c.w >= 0 && x < o0 && y < o1 && z < o2;
-    if (!ok) {
+    const DownCell d = down_cell(indices, i, nb, o0, o1, o2);
+    if (!d.ok) {
       fine_to_coarse[i] = -1;
       continue;
     }
-    const uint64_t key = lin_key(c.x, x, y, z, o0, o1, o2);
-    const uint64_t word = key >> 6;
-    const int32_t v = block_sum[word / kScanBlock] + prefix[word] + __popcll(bitmap[word] & ((1ull << (key & 63)) - 1ull));
+    const uint64_t word = d.key >> 6;
+    const int32_t v = block_sum[word / kScanBlock] + prefix[word] + __popcll(bitmap[word] & ((1ull << (d.key & 63)) - 1ull));
     fine_to_coarse[i] = v;
-    reinterpret_cast<int4*>(out_indices)[v] = make_int4(c.x, x, y, z);  // (every child writes the same row: idempotent)
+    reinterpret_cast<int4*>(out_indices)[v] = d.c;  // (every child writes the same row: idempotent)
   }
 }
 
@@ -509,15 +458,7 @@ __global__ __launch_bounds__(kThreads) void level_counts_kernel(const int32_t* _
     bool is_new = false;
     if (active) {
       const uint64_t key = lin_key(c.x, x, y, z, s0, s1, s2);
-      uint64_t* table = tables + (uint64_t)l * cap;
-      uint64_t slot = mix64(key) & mask;
-      while (true) {
-        const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(table + slot),
-                                                  (unsigned long long)kEmpty, (unsigned long long)key);
-        if (prev == kEmpty) { is_new = true; break; }
-        if (prev == key) break;
-        slot = (slot + 1) & mask;
-      }
+      hash_claim(tables + (uint64_t)l * cap, mask, key, &is_new);
     }
     const uint64_t m = __ballot(is_new);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&wg_new[l], (int)__popcll(m));
@@ -534,10 +475,7 @@ __global__ __launch_bounds__(kThreads) void level_counts_kernel(const int32_t* _
 __global__ __launch_bounds__(kThreads) void identity_rulebook_kernel(int64_t n, int64_t n_tiles, int32_t* __restrict__ rows,
                                                                      int32_t* __restrict__ tile_off, int32_t* __restrict__ nbr,
                                                                      int64_t* __restrict__ num_pairs, const int64_t* __restrict__ n_dev) {
-  if (n_dev) {
-    n = gpn::live_rows(n_dev, n);
-    n_tiles = (n + GPN_TILE_ROWS - 1) / GPN_TILE_ROWS;
-  }
+  live_tiles(n_dev, n, n_tiles);
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i <= n; i += (int64_t)gridDim.x * kThreads) {
     if (i < n) rows[i] = (int32_t)i, nbr[i] = (int32_t)i;
     if (i == n) nbr[n] = -1;
@@ -556,30 +494,7 @@ extern "C" size_t gpn_rulebook_subm3_ws_bytes(int64_t N) {
   w.take<int32_t>(hash_capacity(N));
   w.take<int32_t>(27 * n + 1);
   w.take<int32_t>(27 * n + 64);
-  w.take<char>(scan_temp_bytes(27 * (int64_t)n + 1));
   return w.used;
-}
-
-static int rulebook_subm3_impl(const int32_t* indices, int64_t N, const gpn::DevRows& rows, const int32_t* spatial_shape_host,
-                               int32_t* nbr, int32_t* pair_src, int32_t* pair_dst, int32_t* tile_off, int64_t* num_pairs, void* ws,
-                               size_t ws_bytes, hipStream_t stream);
-
-extern "C" int gpn_rulebook_subm3(const int32_t* indices, int64_t N, const int32_t* spatial_shape_host, int32_t* nbr,
-                                  int32_t* pair_src, int32_t* pair_dst, int32_t* tile_off,
-                                  int64_t* num_pairs, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
-  return rulebook_subm3_impl(indices, N, gpn::DevRows(), spatial_shape_host, nbr, pair_src, pair_dst, tile_off, num_pairs, ws,
-                             ws_bytes, (hipStream_t)stream_);
-}
-
-// the same with the row count on the device: N = the bound every buffer is sized for (workspace from
-// gpn_rulebook_subm3_ws_bytes(N)), *n_dev the live count, n_plan the host's estimate of it (grid sizes only; <= 0: none).
-// Outputs are laid out for the LIVE count (nbr [27][*n_dev] + sentinel, tile_off [27][ceil(*n_dev / 32) + 1]).
-extern "C" int gpn_rulebook_subm3_dev(const int32_t* indices, int64_t N, const int64_t* n_dev, int64_t n_plan,
-                                      const int32_t* spatial_shape_host, int32_t* nbr, int32_t* pair_src, int32_t* pair_dst,
-                                      int32_t* tile_off, int64_t* num_pairs, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
-  GPN_CHECK_ARG(n_dev != nullptr && N >= 1);
-  return rulebook_subm3_impl(indices, N, gpn::DevRows{n_dev, n_plan}, spatial_shape_host, nbr, pair_src, pair_dst, tile_off,
-                             num_pairs, ws, ws_bytes, (hipStream_t)stream_);
 }
 
 static int rulebook_subm3_impl(const int32_t* indices, int64_t N, const gpn::DevRows& rows, const int32_t* spatial_shape_host,
@@ -604,8 +519,6 @@ static int rulebook_subm3_impl(const int32_t* indices, int64_t N, const gpn::Dev
   int32_t* table_ws = w.take<int32_t>(27 * (size_t)N + 1);
   int32_t* table = nbr ? nbr : table_ws;  // the tap-major neighbour table is an output when the caller wants it
   int32_t* pos = w.take<int32_t>(27 * (size_t)N + 64);
-  size_t prim_bytes = scan_temp_bytes(27 * N + 1);
-  void* prim_tmp = w.take<char>(prim_bytes);
   GPN_CHECK_WS(w);
 
   gpn::ProfScope prof(GPN_K_RULEBOOK, stream, 0.0, 16.0 * (double)N + 8.0 * 27.0 * (double)N);
@@ -621,8 +534,25 @@ static int rulebook_subm3_impl(const int32_t* indices, int64_t N, const gpn::Dev
                      dim3(kThreads), 0, stream, indices, N, s0, s1, s2, hkeys, hvals, cap - 1, table,
                      rows.dev);  // (also writes the -1 sentinel table[27 N])
   GPN_CHECK_LAUNCH();
-  return lists_from_table(table, pos, 27, N, pair_src, pair_dst, tile_off, num_pairs, prim_tmp, prim_bytes,
-                          stream, rows);
+  return lists_from_table(table, pos, 27, N, pair_src, pair_dst, tile_off, num_pairs, stream, rows);
+}
+
+extern "C" int gpn_rulebook_subm3(const int32_t* indices, int64_t N, const int32_t* spatial_shape_host, int32_t* nbr,
+                                  int32_t* pair_src, int32_t* pair_dst, int32_t* tile_off,
+                                  int64_t* num_pairs, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
+  return rulebook_subm3_impl(indices, N, gpn::DevRows(), spatial_shape_host, nbr, pair_src, pair_dst, tile_off, num_pairs, ws,
+                             ws_bytes, (hipStream_t)stream_);
+}
+
+// the same with the row count on the device: N = the bound every buffer is sized for (workspace from
+// gpn_rulebook_subm3_ws_bytes(N)), *n_dev the live count, n_plan the host's estimate of it (grid sizes only; <= 0: none).
+// Outputs are laid out for the LIVE count (nbr [27][*n_dev] + sentinel, tile_off [27][ceil(*n_dev / 32) + 1]).
+extern "C" int gpn_rulebook_subm3_dev(const int32_t* indices, int64_t N, const int64_t* n_dev, int64_t n_plan,
+                                      const int32_t* spatial_shape_host, int32_t* nbr, int32_t* pair_src, int32_t* pair_dst,
+                                      int32_t* tile_off, int64_t* num_pairs, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
+  GPN_CHECK_ARG(n_dev != nullptr && N >= 1);
+  return rulebook_subm3_impl(indices, N, gpn::DevRows{n_dev, n_plan}, spatial_shape_host, nbr, pair_src, pair_dst, tile_off,
+                             num_pairs, ws, ws_bytes, (hipStream_t)stream_);
 }
 
 // ================================================================================================ tile order
@@ -632,13 +562,18 @@ static int rulebook_subm3_impl(const int32_t* indices, int64_t N, const gpn::Dev
 // tiles mask-homogeneous while keeping them spatially local: 12.6-18 taps per tile at block_rows = 4096 on the bench
 // scenes.  Outputs: perm[j] = source row of tile position j (padded to a multiple of 16 + 16 entries), and the
 // neighbour table in that order, nbr_p[k][j] = nbr[k][perm[j]].  Stable sort: equal masks keep ascending row order.
+// the K-bit neighbour mask of row j: bit k = the row has a neighbour at tap k
+__device__ __forceinline__ uint32_t tile_order_mask(const int32_t* __restrict__ nbr, int K, int64_t n, int64_t j) {
+  uint32_t m = 0;
+  for (int k = 0; k < K; ++k) m |= (nbr[(int64_t)k * n + j] >= 0 ? 1u : 0u) << k;
+  return m;
+}
+
 __global__ void tile_order_keys_kernel(const int32_t* __restrict__ nbr, int K, int64_t n, int block_shift,
                                        uint64_t* __restrict__ keys, int32_t* __restrict__ vals) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  uint32_t mask = 0;
-  for (int k = 0; k < K; ++k) mask |= (nbr[(int64_t)k * n + j] >= 0 ? 1u : 0u) << k;
-  keys[j] = ((uint64_t)(j >> block_shift) << 32) | mask;
+  keys[j] = ((uint64_t)(j >> block_shift) << 32) | tile_order_mask(nbr, K, n, j);
   vals[j] = (int32_t)j;
 }
 
@@ -686,10 +621,7 @@ __global__ __launch_bounds__(BS) void tile_order_block_sort_kernel(const uint32_
 // the K-bit neighbour mask of every row (whole-chip launch: the table is 4 K n bytes, read coalesced per tap)
 __global__ void tile_order_mask_kernel(const int32_t* __restrict__ nbr, int K, int64_t n, uint32_t* __restrict__ mask) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  uint32_t m = 0;
-  for (int k = 0; k < K; ++k) m |= (nbr[(int64_t)k * n + j] >= 0 ? 1u : 0u) << k;
-  mask[j] = m;
+  if (j < n) mask[j] = tile_order_mask(nbr, K, n, j);
 }
 
 template <int BS, int IPT>
@@ -765,28 +697,6 @@ extern "C" size_t gpn_rulebook_down_ws_bytes(int64_t N) {
   size_t a = sort_temp_bytes(N), b = iscan_temp_bytes(N);
   w.take<char>(a > b ? a : b);
   return w.used;
-}
-
-static int rulebook_down_impl(const int32_t* indices, int64_t N, const gpn::DevRows& rows, int64_t batch_size,
-                              const gpn::DevRows& batch, const int32_t* spatial_shape_host, int32_t* out_indices,
-                              int32_t* fine_to_coarse, int32_t* tap, int64_t* num_out, void* ws, size_t ws_bytes, hipStream_t stream);
-
-extern "C" int gpn_rulebook_down(const int32_t* indices, int64_t N, int64_t batch_size,
-                                 const int32_t* spatial_shape_host, int32_t* out_indices, int32_t* fine_to_coarse, int32_t* tap,
-                                 int64_t* num_out, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
-  return rulebook_down_impl(indices, N, gpn::DevRows(), batch_size, gpn::DevRows(), spatial_shape_host, out_indices, fine_to_coarse,
-                            tap, num_out, ws, ws_bytes, (hipStream_t)stream_);
-}
-
-// row count and batch-entry count (the proposals of a step) on the device: N / batch_size are the bounds the buffers are sized
-// for, *_plan the host's estimates (grid sizes).  Needs the bitmap form (workspace sized for the bounds).
-extern "C" int gpn_rulebook_down_dev(const int32_t* indices, int64_t N, const int64_t* n_dev, int64_t n_plan, int64_t batch_size,
-                                     const int64_t* batch_dev, int64_t batch_plan, const int32_t* spatial_shape_host,
-                                     int32_t* out_indices, int32_t* fine_to_coarse, int32_t* tap, int64_t* num_out, void* ws,
-                                     size_t ws_bytes, gpn_stream_t stream_) {
-  GPN_CHECK_ARG(n_dev != nullptr && N >= 1);
-  return rulebook_down_impl(indices, N, gpn::DevRows{n_dev, n_plan}, batch_size, gpn::DevRows{batch_dev, batch_plan},
-                            spatial_shape_host, out_indices, fine_to_coarse, tap, num_out, ws, ws_bytes, (hipStream_t)stream_);
 }
 
 extern "C" size_t gpn_rulebook_down_dev_ws_bytes(int64_t N, int64_t batch_size, const int32_t* spatial_shape_host) {
@@ -890,40 +800,31 @@ static int rulebook_down_impl(const int32_t* indices, int64_t N, const gpn::DevR
   return GPN_OK;
 }
 
+extern "C" int gpn_rulebook_down(const int32_t* indices, int64_t N, int64_t batch_size,
+                                 const int32_t* spatial_shape_host, int32_t* out_indices, int32_t* fine_to_coarse, int32_t* tap,
+                                 int64_t* num_out, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
+  return rulebook_down_impl(indices, N, gpn::DevRows(), batch_size, gpn::DevRows(), spatial_shape_host, out_indices, fine_to_coarse,
+                            tap, num_out, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+// row count and batch-entry count (the proposals of a step) on the device: N / batch_size are the bounds the buffers are sized
+// for, *_plan the host's estimates (grid sizes).  Needs the bitmap form (workspace sized for the bounds).
+extern "C" int gpn_rulebook_down_dev(const int32_t* indices, int64_t N, const int64_t* n_dev, int64_t n_plan, int64_t batch_size,
+                                     const int64_t* batch_dev, int64_t batch_plan, const int32_t* spatial_shape_host,
+                                     int32_t* out_indices, int32_t* fine_to_coarse, int32_t* tap, int64_t* num_out, void* ws,
+                                     size_t ws_bytes, gpn_stream_t stream_) {
+  GPN_CHECK_ARG(n_dev != nullptr && N >= 1);
+  return rulebook_down_impl(indices, N, gpn::DevRows{n_dev, n_plan}, batch_size, gpn::DevRows{batch_dev, batch_plan},
+                            spatial_shape_host, out_indices, fine_to_coarse, tap, num_out, ws, ws_bytes, (hipStream_t)stream_);
+}
+
 extern "C" size_t gpn_rulebook_down_lists_ws_bytes(int64_t N, int64_t n_out) {
   gpn::WsCarver w(nullptr, 0);
   size_t n = (size_t)(N > 0 ? N : 1), no = (size_t)(n_out > 0 ? n_out : 1);
   w.take<int32_t>(8 * no + 1);
   w.take<int32_t>(8 * n + 1);
   w.take<int32_t>(8 * n + 64);  // scratch of the list builder (shared, sized for the larger table)
-  w.take<char>(scan_temp_bytes(8 * (int64_t)n + 1));
   return w.used;
-}
-
-static int rulebook_down_lists_impl(const int32_t* fine_to_coarse, const int32_t* tap, int64_t N, const gpn::DevRows& rows,
-                                    int64_t n_out, const gpn::DevRows& rows_out, int32_t* fwd_nbr, int32_t* fwd_src, int32_t* fwd_dst,
-                                    int32_t* fwd_tile_off, int32_t* bwd_nbr, int32_t* bwd_src, int32_t* bwd_dst,
-                                    int32_t* bwd_tile_off, int64_t* num_pairs, void* ws, size_t ws_bytes, hipStream_t stream);
-
-extern "C" int gpn_rulebook_down_lists(const int32_t* fine_to_coarse, const int32_t* tap, int64_t N,
-                                       int64_t n_out, int32_t* fwd_nbr, int32_t* fwd_src, int32_t* fwd_dst,
-                                       int32_t* fwd_tile_off, int32_t* bwd_nbr, int32_t* bwd_src, int32_t* bwd_dst,
-                                       int32_t* bwd_tile_off, int64_t* num_pairs, void* ws, size_t ws_bytes,
-                                       gpn_stream_t stream_) {
-  return rulebook_down_lists_impl(fine_to_coarse, tap, N, gpn::DevRows(), n_out, gpn::DevRows(), fwd_nbr, fwd_src, fwd_dst,
-                                  fwd_tile_off, bwd_nbr, bwd_src, bwd_dst, bwd_tile_off, num_pairs, ws, ws_bytes, (hipStream_t)stream_);
-}
-
-// fine and coarse row counts on the device (N, n_out: the bounds; tables laid out for the live counts)
-extern "C" int gpn_rulebook_down_lists_dev(const int32_t* fine_to_coarse, const int32_t* tap, int64_t N, const int64_t* n_dev,
-                                           int64_t n_plan, int64_t n_out, const int64_t* n_out_dev, int64_t n_out_plan,
-                                           int32_t* fwd_nbr, int32_t* fwd_src, int32_t* fwd_dst, int32_t* fwd_tile_off,
-                                           int32_t* bwd_nbr, int32_t* bwd_src, int32_t* bwd_dst, int32_t* bwd_tile_off,
-                                           int64_t* num_pairs, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
-  GPN_CHECK_ARG(n_dev && n_out_dev && N >= 1 && n_out >= 1);
-  return rulebook_down_lists_impl(fine_to_coarse, tap, N, gpn::DevRows{n_dev, n_plan}, n_out, gpn::DevRows{n_out_dev, n_out_plan},
-                                  fwd_nbr, fwd_src, fwd_dst, fwd_tile_off, bwd_nbr, bwd_src, bwd_dst, bwd_tile_off, num_pairs, ws,
-                                  ws_bytes, (hipStream_t)stream_);
 }
 
 static int rulebook_down_lists_impl(const int32_t* fine_to_coarse, const int32_t* tap, int64_t N, const gpn::DevRows& rows,
@@ -949,8 +850,6 @@ static int rulebook_down_lists_impl(const int32_t* fine_to_coarse, const int32_t
   int32_t* tf = fwd_nbr ? fwd_nbr : tf_ws;
   int32_t* tb = bwd_nbr ? bwd_nbr : tb_ws;
   int32_t* pos = w.take<int32_t>(8 * (size_t)N + 64);
-  size_t prim_bytes = scan_temp_bytes(8 * N + 1);
-  void* prim_tmp = w.take<char>(prim_bytes);
   GPN_CHECK_WS(w);
   gpn::ProfScope prof(GPN_K_RULEBOOK, stream, 0.0, 8.0 * (double)N + 16.0 * (double)N);
   const bool dev = rows.dev != nullptr;
@@ -964,21 +863,56 @@ static int rulebook_down_lists_impl(const int32_t* fine_to_coarse, const int32_t
   hipLaunchKernelGGL(down_scatter_tables_kernel, dim3(gpn::dev_grid(gpn::cdiv(N, kThreads), gpn::cdiv(Np, kThreads), dev)), dim3(kThreads), 0,
                      stream, fine_to_coarse, tap, N, n_out, tf, tb, rows.dev, rows_out.dev);
   GPN_CHECK_LAUNCH();
-  int rc = lists_from_table(tf, pos, 8, n_out, fwd_src, fwd_dst, fwd_tile_off, num_pairs, prim_tmp, prim_bytes,
-                            stream, rows_out);
+  int rc = lists_from_table(tf, pos, 8, n_out, fwd_src, fwd_dst, fwd_tile_off, num_pairs, stream, rows_out);
   if (rc != GPN_OK) return rc;
-  return lists_from_table(tb, pos, 8, N, bwd_src, bwd_dst, bwd_tile_off, nullptr, prim_tmp, prim_bytes, stream, rows);
+  return lists_from_table(tb, pos, 8, N, bwd_src, bwd_dst, bwd_tile_off, nullptr, stream, rows);
+}
+
+extern "C" int gpn_rulebook_down_lists(const int32_t* fine_to_coarse, const int32_t* tap, int64_t N,
+                                       int64_t n_out, int32_t* fwd_nbr, int32_t* fwd_src, int32_t* fwd_dst,
+                                       int32_t* fwd_tile_off, int32_t* bwd_nbr, int32_t* bwd_src, int32_t* bwd_dst,
+                                       int32_t* bwd_tile_off, int64_t* num_pairs, void* ws, size_t ws_bytes,
+                                       gpn_stream_t stream_) {
+  return rulebook_down_lists_impl(fine_to_coarse, tap, N, gpn::DevRows(), n_out, gpn::DevRows(), fwd_nbr, fwd_src, fwd_dst,
+                                  fwd_tile_off, bwd_nbr, bwd_src, bwd_dst, bwd_tile_off, num_pairs, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+// fine and coarse row counts on the device (N, n_out: the bounds; tables laid out for the live counts)
+extern "C" int gpn_rulebook_down_lists_dev(const int32_t* fine_to_coarse, const int32_t* tap, int64_t N, const int64_t* n_dev,
+                                           int64_t n_plan, int64_t n_out, const int64_t* n_out_dev, int64_t n_out_plan,
+                                           int32_t* fwd_nbr, int32_t* fwd_src, int32_t* fwd_dst, int32_t* fwd_tile_off,
+                                           int32_t* bwd_nbr, int32_t* bwd_src, int32_t* bwd_dst, int32_t* bwd_tile_off,
+                                           int64_t* num_pairs, void* ws, size_t ws_bytes, gpn_stream_t stream_) {
+  GPN_CHECK_ARG(n_dev && n_out_dev && N >= 1 && n_out >= 1);
+  return rulebook_down_lists_impl(fine_to_coarse, tap, N, gpn::DevRows{n_dev, n_plan}, n_out, gpn::DevRows{n_out_dev, n_out_plan},
+                                  fwd_nbr, fwd_src, fwd_dst, fwd_tile_off, bwd_nbr, bwd_src, bwd_dst, bwd_tile_off, num_pairs, ws,
+                                  ws_bytes, (hipStream_t)stream_);
 }
 
 
-static uint64_t level_table_cap(int64_t n_max) {
-  uint64_t cap = 1024;
-  while (cap < 2 * (uint64_t)(n_max > 0 ? n_max : 1)) cap <<= 1;
-  return cap;
-}
-
+// ================================================================================================ level counts
 extern "C" size_t gpn_rulebook_level_counts_ws_bytes(int64_t n_max, int n_levels) {
-  return gpn::align_up((size_t)level_table_cap(n_max) * (size_t)(n_levels > 0 ? n_levels : 1) * sizeof(uint64_t));
+  return gpn::align_up((size_t)hash_capacity(n_max) * (size_t)(n_levels > 0 ? n_levels : 1) * sizeof(uint64_t));
+}
+
+// one empty hash set per level, one launch; counts are zero already.  The level-0 extent: shape (host) or max_coord_dev.
+// `ws_error` opens the message of a workspace that is too small
+static int level_counts_run(const char* ws_error, const int32_t* indices, int64_t n_max, const int64_t* n_dev, int64_t batch_size,
+                            const int32_t* shape, const int64_t* max_coord_dev, int n_levels, int64_t* counts, void* ws,
+                            size_t ws_bytes, hipStream_t stream) {
+  const uint64_t cap = hash_capacity(n_max);
+  const size_t need = (size_t)cap * (size_t)n_levels * sizeof(uint64_t);
+  if (!ws || ws_bytes < need) {
+    gpn::set_error("%s (%zu needed, %zu given)", ws_error, need, ws_bytes);
+    return GPN_ERR_WS;
+  }
+  GPN_CHECK_HIP(hipMemsetAsync(ws, 0xff, need, stream));
+  gpn::ProfScope prof(GPN_K_RULEBOOK, stream, 0.0, 16.0 * (double)n_max);
+  hipLaunchKernelGGL(level_counts_kernel, dim3((unsigned)gpn::cdiv(n_max, kThreads)), dim3(kThreads), 0, stream, indices, n_max,
+                     n_dev, (int)batch_size, shape ? shape[0] : 0, shape ? shape[1] : 0, shape ? shape[2] : 0, max_coord_dev,
+                     n_levels, static_cast<uint64_t*>(ws), cap, counts);
+  GPN_CHECK_LAUNCH();
+  return GPN_OK;
 }
 
 extern "C" int gpn_rulebook_level_counts(const int32_t* indices, int64_t n_max, const int64_t* n_dev, int64_t batch_size,
@@ -989,19 +923,8 @@ extern "C" int gpn_rulebook_level_counts(const int32_t* indices, int64_t n_max, 
   GPN_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)n_levels, stream));
   if (n_max == 0) return GPN_OK;
   GPN_CHECK_ARG(indices && n_max < (int64_t)0x7fffffff);
-  const uint64_t cap = level_table_cap(n_max);
-  const size_t need = (size_t)cap * (size_t)n_levels * sizeof(uint64_t);
-  if (!ws || ws_bytes < need) {
-    gpn::set_error("gpn_rulebook_level_counts: workspace too small (%zu needed, %zu given)", need, ws_bytes);
-    return GPN_ERR_WS;
-  }
-  GPN_CHECK_HIP(hipMemsetAsync(ws, 0xff, need, stream));
-  gpn::ProfScope prof(GPN_K_RULEBOOK, stream, 0.0, 16.0 * (double)n_max);
-  hipLaunchKernelGGL(level_counts_kernel, dim3((unsigned)gpn::cdiv(n_max, kThreads)), dim3(kThreads), 0, stream, indices, n_max,
-                     n_dev, (int)batch_size, spatial_shape_host[0], spatial_shape_host[1], spatial_shape_host[2], nullptr, n_levels,
-                     static_cast<uint64_t*>(ws), cap, counts);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  return level_counts_run("gpn_rulebook_level_counts: workspace too small", indices, n_max, n_dev, batch_size, spatial_shape_host,
+                          nullptr, n_levels, counts, ws, ws_bytes, stream);
 }
 
 // the same with the row count and the level-0 extent still on the device (gpn_voxelize_scenes: no host read in between);
@@ -1010,39 +933,29 @@ int gpn::rulebook_level_counts_dev(const int32_t* indices, int64_t n_max, const 
                                    const int64_t* max_coord_dev, int n_levels, int64_t* counts, void* ws, size_t ws_bytes,
                                    hipStream_t stream) {
   GPN_CHECK_ARG(indices && n_dev && max_coord_dev && counts && n_levels >= 1 && n_levels <= 16 && n_max >= 1);
-  const uint64_t cap = level_table_cap(n_max);
-  const size_t need = (size_t)cap * (size_t)n_levels * sizeof(uint64_t);
-  if (!ws || ws_bytes < need) {
-    gpn::set_error("gpn_voxelize_scenes: workspace too small for the level counts (%zu needed, %zu given)", need, ws_bytes);
-    return GPN_ERR_WS;
-  }
-  GPN_CHECK_HIP(hipMemsetAsync(ws, 0xff, need, stream));
-  gpn::ProfScope prof(GPN_K_RULEBOOK, stream, 0.0, 16.0 * (double)n_max);
-  hipLaunchKernelGGL(level_counts_kernel, dim3((unsigned)gpn::cdiv(n_max, kThreads)), dim3(kThreads), 0, stream, indices, n_max,
-                     n_dev, (int)batch_size, 0, 0, 0, max_coord_dev, n_levels, static_cast<uint64_t*>(ws), cap, counts);
+  return level_counts_run("gpn_voxelize_scenes: workspace too small for the level counts", indices, n_max, n_dev, batch_size,
+                          nullptr, max_coord_dev, n_levels, counts, ws, ws_bytes, stream);
+}
+
+// ================================================================================================ identity
+// rows.dev: a device-counted row count (n = the bound of the buffers)
+static int rulebook_identity_run(int64_t n, const gpn::DevRows& rows, int32_t* out_rows, int32_t* tile_off, int32_t* nbr,
+                                 int64_t* num_pairs, hipStream_t stream) {
+  const int64_t wgs = gpn::cdiv(n + 1, (int64_t)kThreads), plan_wgs = gpn::cdiv(gpn::plan_rows(n, rows) + 1, (int64_t)kThreads);
+  hipLaunchKernelGGL(identity_rulebook_kernel, dim3(gpn::dev_grid(wgs, plan_wgs, rows.dev != nullptr)), dim3(kThreads), 0, stream, n,
+                     gpn::cdiv(n, (int64_t)GPN_TILE_ROWS), out_rows, tile_off, nbr, num_pairs, rows.dev);
   GPN_CHECK_LAUNCH();
   return GPN_OK;
 }
 
 extern "C" int gpn_rulebook_identity(int64_t n, int32_t* rows, int32_t* tile_off, int32_t* nbr, int64_t* num_pairs,
                                      gpn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   GPN_CHECK_ARG(n >= 0 && n < (int64_t)0x7fffffff && rows && tile_off && nbr && num_pairs);
-  const int64_t n_tiles = gpn::cdiv(n, (int64_t)GPN_TILE_ROWS);
-  hipLaunchKernelGGL(identity_rulebook_kernel, dim3((unsigned)gpn::cdiv(n + 1, (int64_t)kThreads)), dim3(kThreads), 0, stream, n,
-                     n_tiles, rows, tile_off, nbr, num_pairs, (const int64_t*)nullptr);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  return rulebook_identity_run(n, gpn::DevRows(), rows, tile_off, nbr, num_pairs, (hipStream_t)stream_);
 }
 
-// the same for a device-counted row count (n = the bound of the buffers)
 extern "C" int gpn_rulebook_identity_dev(int64_t n, const int64_t* n_dev, int64_t n_plan, int32_t* rows, int32_t* tile_off,
                                          int32_t* nbr, int64_t* num_pairs, gpn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   GPN_CHECK_ARG(n >= 1 && n < (int64_t)0x7fffffff && n_dev && rows && tile_off && nbr && num_pairs);
-  const int64_t np = gpn::plan_rows(n, gpn::DevRows{n_dev, n_plan});
-  hipLaunchKernelGGL(identity_rulebook_kernel, dim3(gpn::dev_grid(gpn::cdiv(n + 1, (int64_t)kThreads), gpn::cdiv(np + 1, (int64_t)kThreads), true)),
-                     dim3(kThreads), 0, stream, n, gpn::cdiv(n, (int64_t)GPN_TILE_ROWS), rows, tile_off, nbr, num_pairs, n_dev);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  return rulebook_identity_run(n, gpn::DevRows{n_dev, n_plan}, rows, tile_off, nbr, num_pairs, (hipStream_t)stream_);
 }

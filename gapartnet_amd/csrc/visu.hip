@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "gpn_common.h"
+#include "wg_scan.h"
 
 namespace {
 
@@ -64,31 +65,8 @@ __device__ __forceinline__ uint8_t to_u8(float f) {
 // rank[m] = number of true mask entries before m: one workgroup, tiles of kScanThreads entries
 __global__ __launch_bounds__(kScanThreads) void visu_rank_kernel(const uint8_t* __restrict__ mask, int64_t M,
                                                                  int32_t* __restrict__ rank) {
-  __shared__ int wsum[kScanWaves];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int base = 0;
-  for (int64_t t0 = 0; t0 < M; t0 += kScanThreads) {
-    const int64_t m = t0 + tid;
-    const int c = (m < M && mask[m]) ? 1 : 0;
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScanWaves; ++w) {
-      const int s = wsum[w];
-      before += w < wave ? s : 0;
-      total += s;
-    }
-    if (m < M) rank[m] = base + before + incl - c;
-    base += total;
-    __syncthreads();  // wsum is rewritten by the next tile
-  }
+  __shared__ int32_t wsum[kScanWaves];
+  gpn::block_scan_tiled<kScanWaves>(M, [&](int64_t m) { return mask[m] ? 1 : 0; }, rank, wsum);
 }
 
 // row of proposal point m in the batch's point matrix, -1 if an index is out of range

@@ -8,6 +8,7 @@
 // bit-identical to the CPU oracle and run-to-run deterministic (no fp atomics).  Voxels come out in
 // ascending key order, which is also the row order that gives the sparse-conv gathers their locality.
 #include "gpn_common.h"  // first: pulls <cstring> ahead of the HIP/rocPRIM headers
+#include "wg_scan.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -487,7 +488,7 @@ __global__ __launch_bounds__(256) void voxb_mark_kernel(const float* __restrict_
 template <bool POP>
 __global__ __launch_bounds__(256) void voxb_scan_sums_kernel(const uint32_t* __restrict__ v, const unsigned* __restrict__ n_dev,
                                                              int64_t n_max, uint32_t* __restrict__ block_sum) {
-  __shared__ uint32_t part[256];
+  __shared__ uint32_t wsum[4];
   const int64_t n = n_dev ? (int64_t)*n_dev : n_max;
   const int64_t base = (int64_t)blockIdx.x * kScanBlock;
   uint32_t acc = 0;
@@ -495,49 +496,26 @@ __global__ __launch_bounds__(256) void voxb_scan_sums_kernel(const uint32_t* __r
     const int64_t w = base + k;
     if (w < n) acc += POP ? (uint32_t)__popc(v[w]) : v[w];
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) block_sum[blockIdx.x] = base < n ? part[0] : 0u;
+  acc = gpn::block_sum<4>(acc, wsum);
+  if (threadIdx.x == 0) block_sum[blockIdx.x] = acc;
 }
 // B: one workgroup scans the block sums in place (exclusive) and leaves the total in *total_out
 __global__ __launch_bounds__(1024) void voxb_scan_blocks_kernel(uint32_t* __restrict__ block_sum, int64_t n_blocks,
                                                                 const unsigned* __restrict__ n_dev, int64_t* __restrict__ total_out) {
-  __shared__ uint32_t part[1024];
-  __shared__ uint32_t carry;
+  __shared__ uint32_t wsum[16];
   if (n_dev) {  // (only the blocks that hold live values: the others' sums are zero and their bases are never read)
     const int64_t live = ((int64_t)*n_dev + kScanBlock - 1) / kScanBlock;
     n_blocks = live < n_blocks ? live : n_blocks;
   }
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < n_blocks; b0 += 1024) {
-    const int64_t b = b0 + threadIdx.x;
-    const uint32_t x = b < n_blocks ? block_sum[b] : 0u;
-    part[threadIdx.x] = x;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan
-      const uint32_t t = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (b < n_blocks) block_sum[b] = carry + part[threadIdx.x] - x;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += part[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && total_out) *total_out = (int64_t)carry;
+  const uint32_t total = gpn::block_scan_tiled<16>(n_blocks, [&](int64_t b) { return block_sum[b]; }, block_sum, wsum);
+  if (threadIdx.x == 0 && total_out) *total_out = (int64_t)total;
 }
 // C: exclusive prefix of every value (block base + scan inside the block)
 template <bool POP>
 __global__ __launch_bounds__(256) void voxb_scan_apply_kernel(const uint32_t* __restrict__ v, const unsigned* __restrict__ n_dev,
                                                               int64_t n_max, const uint32_t* __restrict__ block_base,
                                                               uint32_t* __restrict__ prefix, int32_t* __restrict__ tail_out) {
-  __shared__ uint32_t part[256];
+  __shared__ uint32_t wsum[4];
   const int64_t n = n_dev ? (int64_t)*n_dev : n_max;
   const int64_t base = (int64_t)blockIdx.x * kScanBlock;
   if (base >= n) return;
@@ -549,15 +527,8 @@ __global__ __launch_bounds__(256) void voxb_scan_apply_kernel(const uint32_t* __
     x[k] = w < n ? (POP ? (uint32_t)__popc(v[w]) : v[w]) : 0u;
     acc += x[k];
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    const uint32_t t = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += t;
-    __syncthreads();
-  }
-  uint32_t run = block_base[blockIdx.x] + part[threadIdx.x] - acc;
+  uint32_t total;
+  uint32_t run = block_base[blockIdx.x] + gpn::block_scan<4>(acc, wsum, &total) - acc;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int64_t w = base + (int64_t)threadIdx.x * PER + k;

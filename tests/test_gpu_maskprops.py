@@ -187,3 +187,25 @@ def test_one_large_scene_crosses_every_per_pass_word_limit(cuda):
     masks = [rng.rand(1, 70000) < 0.5]
     built = _check(cuda, counts, masks, [np.array([4])], _xyz(counts, 15, cuda))
     assert built["M"] == int(masks[0].sum()) and built["P"] == 1
+
+
+def test_more_masks_than_one_tile_of_the_mask_scan(cuda):
+    """1025 masks over a scene of 64 points, min_points = 1: the number of a kept mask, its first member slot and the count of
+    unknown labels are carried across the 1024-mask tiles of the one-workgroup scan (the last mask sits in the second tile)"""
+    from gapartnet_amd import _C
+    counts, K = [64], 1025
+    rng = np.random.RandomState(16)
+    masks = [rng.rand(K, 64) < rng.choice([0.0, 0.02, 0.05], size=(K, 1))]
+    masks[0][[0, 1023, 1024]] = False
+    masks[0][0, :3] = masks[0][1023, 5:7] = masks[0][1024, 60:] = True
+    sizes = masks[0].sum(1)
+    assert (sizes == 0).sum() > 100 and (sizes > 0).sum() > 500 and sizes.max() < 12, "masks of a few points, many of them dropped"
+    labels = [rng.randint(1, N_CLASSES, size=K)]
+    xyz = _xyz(counts, 17, cuda)
+    built = _check(cuda, counts, masks, labels, xyz, min_points=1)
+    assert built["P"] == int((sizes > 0).sum()) and built["proposal_mask"][-1] == 1024 and built["sizes"][-1] == 4
+    labels[0][[3, 1023, 1024]] = [0, N_CLASSES, -1]
+    with pytest.raises(ValueError, match="label"):
+        MR.stage(xyz, counts, masks, labels, 1, N_CLASSES)
+    with pytest.raises(_C.GpnError, match="^proposals_from_masks: 3 mask"):
+        _run(cuda, counts, masks, labels, xyz, min_points=1)

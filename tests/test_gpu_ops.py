@@ -173,18 +173,23 @@ def test_scene_batch_voxelisation_with_one_host_read(H, cuda):
     assert out[5] is None and out[0].shape[0] > 3900 and max(out[2]) > 1024
 
 
-@pytest.mark.parametrize("case", ["bench", "ragged", "heavy", "dropped", "one_point"])
+@pytest.mark.parametrize("case", ["bench", "ragged", "heavy", "dropped", "one_point", "many_blocks"])
 def test_sort_free_scene_voxelisation_equals_the_sorting_form(H, cuda, case):
     """gpn_voxelize_scenes (round 5: occupancy bitmap in key order + popcount ranks + counting placement, no sort) against
     gpn_voxelize_scenes_sorted (stable radix sort of packed keys; pinned to the oracle through the per-call path): voxel order,
     point -> voxel map, the points-by-voxel CSR (ascending point order inside a voxel, dropped points last), ordered means,
     extent, dropped count and the coarse levels' row counts - all EQUAL.  Cases: the bench's batch, ragged scene sizes, voxels
-    holding hundreds of points, points that are dropped (NaN coordinates), a one-point scene."""
-    rng = np.random.default_rng({"bench": 1, "ragged": 2, "heavy": 3, "dropped": 4, "one_point": 5}[case])
+    holding hundreds of points, points that are dropped (NaN coordinates), a one-point scene, and five sparse scenes of 193 cells
+    per axis: a bitmap of 1.12 M words = 1097 blocks of 1024, more than one tile of the one-workgroup scan of the block sums."""
+    rng = np.random.default_rng({"bench": 1, "ragged": 2, "heavy": 3, "dropped": 4, "one_point": 5, "many_blocks": 6}[case])
     counts = {"bench": [20000] * 8, "ragged": [3000, 1, 4500, 777, 12000], "heavy": [6000, 6000], "dropped": [5000, 4000, 3000],
-              "one_point": [1]}[case]
+              "one_point": [1], "many_blocks": [2000] * 5}[case]
     M = sum(counts)
-    xyz = rng.uniform(-0.5, 0.5, (M, 3)).astype(np.float32)
+    half = 0.96 if case == "many_blocks" else 0.5
+    xyz = rng.uniform(-half, half, (M, 3)).astype(np.float32)
+    if case == "many_blocks":
+        cells = [int(np.floor((np.ptp(xyz[:, a].astype(np.float64))) / 0.01)) for a in range(3)]  # (a lower bound of the grid)
+        assert 1024 * 1024 * 32 < 5 * cells[0] * cells[1] * cells[2] and 5 * 194 ** 3 < 2 ** 27 and max(cells) < 1024
     if case == "heavy":
         xyz[::2] = np.round(xyz[::2] * 4) / 4 + 0.003   # a few hundred points per voxel on a coarse lattice
     if case == "dropped":
@@ -436,6 +441,21 @@ def test_ball_query_and_ccl(H, cuda, K, labels):
     for compacted in (False, True):
         got = host(H.ccl(dev(be, cuda), idx.reshape(-1), compacted))
         assert np.array_equal(got, O.ccl(be, ref_idx.reshape(-1), compacted))
+
+
+@pytest.mark.parametrize("Q", [1, 1023, 1024, 1025, 2049])
+def test_ccl_compacted_labels_across_the_rank_scan_tiles(H, cuda, Q):
+    """vertices 2 i and 2 i + 1 joined (an odd Q leaves the last one alone): every second vertex is a root, and the ranks of the
+    roots - the compacted labels - are carried across the 1024-entry tiles of the one-workgroup scan from Q = 1025 on"""
+    v = np.arange(Q, dtype=np.int32)
+    has = (v ^ 1) < Q
+    end = np.cumsum(has).astype(np.int32)
+    be = np.stack([end - has, end], 1).reshape(-1)
+    edges = (v ^ 1)[has]
+    for compacted in (False, True):
+        want = O.ccl(be, edges, compacted)
+        assert np.array_equal(host(H.ccl(dev(be, cuda), dev(edges, cuda), compacted)), want)
+    assert np.array_equal(want, v // 2)
 
 
 def test_ball_query_unsorted_batches_and_empty_segment(H, cuda):
@@ -700,7 +720,7 @@ def test_grid_ball_query_is_bit_exact(H, cuda, case):
         assert (ref_cnt == K).mean() > 0.5, "the dense case must exercise truncation"
 
 
-@pytest.mark.parametrize("block", [16384, 8192, 4096, 1024])
+@pytest.mark.parametrize("block", [16384, 8192, 4096, 1024, 512])
 def test_tile_order_is_the_stable_sort_by_neighbour_mask(H, cuda, block):
     """gpn_rulebook_tile_order: inside every block of `block` rows the rows are ordered by their K-bit neighbour mask, equal
     masks in ascending row order (blocks of 4096 / 8192 / 16384 rows are sorted in one workgroup's LDS, other sizes by the
@@ -711,7 +731,7 @@ def test_tile_order_is_the_stable_sort_by_neighbour_mask(H, cuda, block):
     shape = [96, 96, 96]
     idx = dev(synth.surface_indices(rng, 3, shape, 7000), cuda)
     n = idx.shape[0]
-    assert n % 16 != 0, "a ragged last tile: the padding checks below need one (all four seeds give one)"
+    assert n % 16 != 0, "a ragged last tile: the padding checks below need one (all five seeds give one)"
     rb = H.rulebook_subm3(idx, shape)
     K = 27
     perm = torch.empty(((n + 15) // 16 * 16 + 16,), dtype=torch.int32, device=cuda)

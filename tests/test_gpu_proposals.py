@@ -124,16 +124,16 @@ def test_fused_npcs_loss_equals_the_torch_formulation(cuda, n_props, seed):
     assert torch.allclose(g0, g1, rtol=1e-4, atol=1e-7), float((g0 - g1).abs().max())
 
 
-@pytest.mark.parametrize("seed,full", [(0, 28.0), (1, 28.0), (2, 7.0)])
+@pytest.mark.parametrize("seed,full", [(0, 28.0), (1, 28.0), (2, 7.0), (3, 28.0)])
 def test_revoxelisation_without_a_sort_equals_the_sorting_voxeliser(cuda, seed, full):
     """gpn_proposals_revoxelize (one workgroup per proposal: LDS bitmap, popcount ranks, stable placement) against
     gpn_voxelize_ex (keys + radix sort) on the same grouped points: unique cells, voxel of every point, point order, CSR -
     with points outside their grid, many points per cell, proposals of 1 ... 3000 points, empty tail rows, unused proposal
-    slots"""
+    slots; seed 3: 1025 proposals of two points behind the others - more than one 1024-proposal tile of the scan of their bases"""
     import ctypes
     from gapartnet_amd import _C, hip_ops as H
     rng = np.random.default_rng(seed)
-    sizes = [1, 5, 7, 3000, 257, 256, 255, 64, 1000] + [int(n) for n in rng.integers(5, 400, size=40)]
+    sizes = [1, 5, 7, 3000, 257, 256, 255, 64, 1000] + [int(n) for n in rng.integers(5, 400, size=40)] + [2] * (1025 if seed == 3 else 0)
     P, T = len(sizes), int(sum(sizes))
     P_ub, T2 = P + 23, T + 517
     off = np.full(P_ub + 1, T, np.int64)

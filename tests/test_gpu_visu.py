@@ -177,6 +177,20 @@ def test_scene_maps_equal_the_torch_formulation(cuda):
     assert ins.shape == (30,) and not ins.any()
 
 
+@pytest.mark.parametrize("M", [1023, 1024, 1025, 2049])
+def test_scene_maps_across_the_rank_scan_tiles(cuda, M):
+    """M proposal points, every second one NPCS-valid: the rank of a valid point - its row of npcs_preds - is carried across the
+    1024-entry tiles of the one-workgroup scan from M = 1025 on"""
+    from gapartnet_amd.inference import scene_maps_torch
+    rng = np.random.default_rng(M)
+    rows = rng.permutation(M + 50)[:M].tolist()
+    valid = (np.arange(M) % 2 == 0).tolist()
+    case = _maps_case(rng, M + 50, [rows[:M // 3], rows[M // 3:]], [valid[:M // 3], valid[M // 3:]])
+    got = _check_maps(cuda, case)
+    for g, w in zip(got, scene_maps_torch(*[torch.as_tensor(a) for a in case[:5]], case[5])):
+        assert np.array_equal(g, w.numpy())
+
+
 # ---------------------------------------------------------------------------------------------------- predictions and boxes
 def _part(rng, n, noise=0.002):
     """camera-frame points of a part and their NPCS (a similarity apart, plus noise)"""
