@@ -50,6 +50,9 @@ const char* kEntryPoints[] = {
     "gpn_mask_pack", "gpn_proposals_from_masks_ws_bytes", "gpn_proposals_from_masks",
     "gpn_frame_backproject", "gpn_frame_select_ws_bytes", "gpn_frame_select",
     "gpn_cloud_grid_sample_ws_bytes", "gpn_cloud_grid_sample",
+    "gpn_frame_candidates", "gpn_frame_plane_hypotheses", "gpn_frame_plane_score", "gpn_frame_plane_winner",
+    "gpn_frame_plane_refit_ws_bytes", "gpn_frame_plane_refit", "gpn_frame_plane_cut", "gpn_frame_components",
+    "gpn_frame_component_select_ws_bytes", "gpn_frame_component_select",
     "gpn_joint_sample", "gpn_cpd_rigid", "gpn_joint_from_rigid",
     "gpn_pose_gt_fit", "gpn_box_iou_3d", "gpn_pose_pair_errors",
     "gpn_render_max_links", "gpn_render_ws_bytes", "gpn_render_setup", "gpn_render_raster", "gpn_render_annotate",

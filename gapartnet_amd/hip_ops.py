@@ -1850,6 +1850,151 @@ def frame_prepare(depth, rgb, K, m, cap, seeds, keep=None, depth_scale=1.0, flip
     return got
 
 
+# ---------------------------------------------------------------------------------------------------- OB (object isolation)
+ISOLATE_OK, ISOLATE_NO_PLANE, ISOLATE_EMPTY = 0, 1, 2
+ISOLATE_SELECT = {"largest": 0, "center": 1, "all": 2}
+ISOLATE_MAX_PLANES, ISOLATE_MAX_HYP, ISOLATE_TRIES = 4, 1024, 8
+_dbl = _C.ctypes.c_double
+
+
+def _frame_dims(t):
+    if t.dim() != 3:
+        raise _C.GpnError(f"a per-pixel frame tensor must be [V,H,W], got {tuple(t.shape)}")
+    return (int(v) for v in t.shape)
+
+
+def frame_candidates(rows, valid, z_min=0.0, z_max=float("inf")):
+    """cand [V,H,W] u8 = valid && z_min <= |z| <= z_max (include/gpn.h section OB)"""
+    dev = _dev(rows, valid)
+    V, H, W = _frame_dims(valid)
+    cand = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    check(_C.lib().gpn_frame_candidates(ptr(rows), ptr(valid), i32(V), i32(H), i32(W), _dbl(float(z_min)), _dbl(float(z_max)), ptr(cand),
+                                        _stream()), "gpn_frame_candidates")
+    return cand
+
+
+def frame_plane_hypotheses(rows, cand, pix, valid_counts, seeds, n_hyp=256, round=0):
+    """stage 1: -> (hyp [V, n_hyp, 4] f64, NaN where degenerate; hyp_pix [V, n_hyp] i32 = the pixel of p0 or -1); ``seeds``: [V]
+    uint32 values or the int32 tensor of them"""
+    dev = _dev(rows, cand, pix, valid_counts)
+    V, H, W = _frame_dims(cand)
+    seeds = seeds if torch.is_tensor(seeds) else _seed_tensor(seeds, V, dev)
+    n_hyp = int(n_hyp)
+    hyp = torch.empty((V, max(n_hyp, 0), 4), dtype=torch.float64, device=dev)
+    hyp_pix = torch.empty((V, max(n_hyp, 0)), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_frame_plane_hypotheses(ptr(rows), ptr(cand), ptr(pix), ptr(valid_counts), ptr(seeds), i32(V), i32(H), i32(W),
+                                              i32(n_hyp), i32(round), ptr(hyp), ptr(hyp_pix), _stream()), "gpn_frame_plane_hypotheses")
+    return hyp, hyp_pix
+
+
+def frame_plane_score(rows, cand, hyp, tol, variant=0):
+    """stage 2: counts [V, n_hyp] i32 = the candidates within ``tol`` of every hypothesis"""
+    dev = _dev(rows, cand, hyp)
+    V, H, W = _frame_dims(cand)
+    n_hyp = int(hyp.shape[1])
+    counts = torch.empty((V, n_hyp), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_frame_plane_score(ptr(rows), ptr(cand), ptr(hyp), i32(V), i32(H), i32(W), i32(n_hyp), _dbl(float(tol)),
+                                         i32(variant), ptr(counts), _stream()), "gpn_frame_plane_score")
+    return counts
+
+
+def frame_plane_winner(counts):
+    """winner [V] i32: the hypothesis of the largest count, ties to the lowest; -1 when every count is 0"""
+    dev = _dev(counts)
+    V, n_hyp = (int(v) for v in counts.shape)
+    winner = torch.empty((V,), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_frame_plane_winner(ptr(counts), i32(V), i32(n_hyp), ptr(winner), _stream()), "gpn_frame_plane_winner")
+    return winner
+
+
+def frame_plane_refit(rows, cand, hyp, hyp_pix, winner, tol, min_plane_fraction=0.1, round=0, max_planes=1, planes=None,
+                      plane_inliers=None, n_planes=None):
+    """stage 3: refit the winner on its inliers and accept it or not -> (planes [V, max_planes, 4] f64, plane_inliers
+    [V, max_planes] i32, n_planes [V] i32); entry ``round`` is written (pass the three tensors of round 0 to the later rounds)"""
+    dev = _dev(rows, cand, hyp, hyp_pix, winner)
+    V, H, W = _frame_dims(cand)
+    max_planes = int(max_planes)
+    if planes is None:
+        planes = torch.full((V, max(max_planes, 1), 4), float("nan"), dtype=torch.float64, device=dev)
+        plane_inliers = torch.zeros((V, max(max_planes, 1)), dtype=torch.int32, device=dev)
+        n_planes = torch.zeros((V,), dtype=torch.int32, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_frame_plane_refit_ws_bytes(i32(V), i32(H), i32(W)), dev)
+    check(L.gpn_frame_plane_refit(ptr(rows), ptr(cand), ptr(hyp), ptr(hyp_pix), ptr(winner), i32(V), i32(H), i32(W), i32(hyp.shape[1]),
+                                  _dbl(float(tol)), _dbl(float(min_plane_fraction)), i32(round), i32(max_planes), ptr(planes),
+                                  ptr(plane_inliers), ptr(n_planes), ptr(ws), szt(ws.numel()), _stream()), "gpn_frame_plane_refit")
+    return planes, plane_inliers, n_planes
+
+
+def frame_plane_cut(rows, cand, planes, tol, round=0):
+    """stage 4, IN PLACE on ``cand``: under an accepted plane of ``round`` only what lies more than ``tol`` on the camera's side stays"""
+    _dev(rows, cand, planes)
+    V, H, W = _frame_dims(cand)
+    check(_C.lib().gpn_frame_plane_cut(ptr(rows), ptr(planes), i32(V), i32(H), i32(W), i32(planes.shape[1]), i32(round), _dbl(float(tol)),
+                                       ptr(cand), _stream()), "gpn_frame_plane_cut")
+    return cand
+
+
+def frame_components(rows, cand, jump_abs=0.01, jump_rel=0.01, min_pixels=6):
+    """stage 5: 4-connected components with the depth-continuity rule -> (labels [V,H,W] i32 = the component's smallest pixel, -1
+    off the candidates; sizes [V, H*W] i32 at the roots; n_components [V] i32 of at least ``min_pixels`` pixels)"""
+    dev = _dev(rows, cand)
+    V, H, W = _frame_dims(cand)
+    labels = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+    sizes = torch.empty((V, H * W), dtype=torch.int32, device=dev)
+    n_comp = torch.empty((V,), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_frame_components(ptr(rows), ptr(cand), i32(V), i32(H), i32(W), _dbl(float(jump_abs)), _dbl(float(jump_rel)),
+                                        i32(min_pixels), ptr(labels), ptr(sizes), ptr(n_comp), _stream()), "gpn_frame_components")
+    return labels, sizes, n_comp
+
+
+def frame_component_select(labels, sizes, n_planes, select="largest", min_pixels=6, anchor=None):
+    """stage 6: -> (keep [V,H,W] u8, chosen [V] i32 = the root or -1, status [V] i32 = ISOLATE_OK / _NO_PLANE / _EMPTY); ``anchor``
+    [V,2] i32 (column, line) for select "center\""""
+    dev = _dev(labels, sizes, n_planes, anchor)
+    V, H, W = _frame_dims(labels)
+    if select not in ISOLATE_SELECT:
+        raise ValueError(f"select must be one of {tuple(ISOLATE_SELECT)}, got {select!r}")
+    anchor = _c(anchor, torch.int32)
+    if anchor is not None and anchor.numel() != V * 2:
+        raise _C.GpnError("frame_component_select: anchor must be [V,2]")
+    keep = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    chosen = torch.empty((V,), dtype=torch.int32, device=dev)
+    status = torch.empty((V,), dtype=torch.int32, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_frame_component_select_ws_bytes(i32(V)), dev)
+    check(L.gpn_frame_component_select(ptr(labels), ptr(sizes), ptr(n_planes), ptr(anchor), i32(V), i32(H), i32(W),
+                                       i32(ISOLATE_SELECT[select]), i32(min_pixels), ptr(keep), ptr(chosen), ptr(status), ptr(ws),
+                                       szt(ws.numel()), _stream()), "gpn_frame_component_select")
+    return keep, chosen, status
+
+
+def frame_isolate(rows, valid, valid_counts, seeds, max_planes=1, n_hyp=256, tol=0.005, min_plane_fraction=0.1, z_min=0.0,
+                  z_max=float("inf"), jump_abs=0.01, jump_rel=0.01, select="largest", min_pixels=6, anchor=None):
+    """the whole of section OB on what frame_backproject returned: candidates, ``max_planes`` rounds of hypotheses / score / winner /
+    refit / cut, components, select.  No host read.  -> dict(keep, labels, sizes, planes, plane_inliers, n_planes, n_components,
+    chosen, status), all on the device"""
+    dev = _dev(rows, valid, valid_counts)
+    V, H, W = _frame_dims(valid)
+    seeds_t = _seed_tensor(seeds, V, dev)
+    # (cap == 0: pix = the valid pixels ascending; the packed rows are not needed here)
+    _, pix, _, _ = frame_select(rows, valid, valid_counts, np.asarray(seeds, dtype=np.int64), 0)
+    cand = frame_candidates(rows, valid, z_min, z_max)
+    planes = inl = n_planes = None
+    for r in range(int(max_planes)):
+        hyp, hyp_pix = frame_plane_hypotheses(rows, cand, pix, valid_counts, seeds_t, n_hyp, r)
+        winner = frame_plane_winner(frame_plane_score(rows, cand, hyp, tol))
+        planes, inl, n_planes = frame_plane_refit(rows, cand, hyp, hyp_pix, winner, tol, min_plane_fraction, r, max_planes, planes, inl,
+                                                  n_planes)
+        frame_plane_cut(rows, cand, planes, tol, r)
+    if planes is None:
+        raise ValueError("max_planes must be at least 1")
+    labels, sizes, n_comp = frame_components(rows, cand, jump_abs, jump_rel, min_pixels)
+    keep, chosen, status = frame_component_select(labels, sizes, n_planes, select, min_pixels, anchor)
+    return dict(keep=keep, labels=labels, sizes=sizes, planes=planes, plane_inliers=inl, n_planes=n_planes, n_components=n_comp,
+                chosen=chosen, status=status, cand=cand)
+
+
 # ---------------------------------------------------------------------------------------------------- JE (joint estimation)
 JOINT_TYPES = {"revolute": 0, "prismatic": 1}
 

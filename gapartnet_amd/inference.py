@@ -19,6 +19,8 @@ end tools/visu_utils.py:141-173 ``OBJfile2points`` / ``FindMaxDis`` / ``WorldSpa
                      image with the boxes drawn out (csrc/frameprep.hip; include/gpn.h section FR)
 ``python -m gapartnet_amd.inference --ckpt X --depth d.npy|d.png --rgb i.png --intrinsics K.txt|K.npy [--depth_scale 1000
         --keep_mask m.png --flip --presample 4 --seed 0 --sampler grid --masks a.npz] --out DIR``   writes DIR/<name>.npz and DIR/<name>_overlay.png
+        ``--isolate [--isolate_planes N --plane_tol T --isolate_select largest|center|all --z_max Z]``: raw frames - the object is
+        cut out first (``isolate_objects``; csrc/isolate.hip, include/gpn.h section OB); the ``.npz`` gains ``keep``, ``planes``, ``isolate_status``
         (``--masks``: ``masks`` [K, H, W] and ``labels`` [K] per frame); frames of different sizes go in separate batches
         ``--bank bank.npy --features f0.npy ...`` next to ``--masks``: class-agnostic masks (a segmenter's) - the ``.npz`` may omit
         ``labels``; each mask's class is a 5-nearest-neighbour vote of its pooled image feature against the bank
@@ -53,6 +55,7 @@ class PreparedClouds:
     source: torch.Tensor        # [M, C] f32: the caller's clouds, concatenated
     table: Optional[dict] = None  # device tables gpn_cloud_nearest reads (CUDA only)
     level: Optional[torch.Tensor] = None  # [S] i64 (host), sampler "grid" only: the octree level used, -1 where a cloud was not sampled
+    isolation: Optional["ObjectIsolation"] = None  # ``prepare_frames(isolate=...)`` only
 
 
 # ---------------------------------------------------------------------------------------------------- torch formulation (CPU)
@@ -332,23 +335,259 @@ def _check_frames(depth, rgb, K, keep):
     return depth, rgb, K, keep
 
 
+# ---------------------------------------------------------------------------------------------------- object isolation
+ISOLATE_OK, ISOLATE_NO_PLANE, ISOLATE_EMPTY = 0, 1, 2  # (include/gpn.h section OB)
+ISOLATE_STATUS_NAMES = {ISOLATE_OK: "ok", ISOLATE_NO_PLANE: "no plane", ISOLATE_EMPTY: "empty"}
+ISOLATE_SELECT = ("largest", "center", "all")
+_ISOLATE_MAX_PLANES, _ISOLATE_MAX_HYP, _ISOLATE_TRIES = 4, 1024, 8
+
+
+@dataclass
+class IsolateConfig:
+    """the parameters of include/gpn.h section OB; lengths in the units of the rows (depth / depth_scale)"""
+    max_planes: int = 1                 # RANSAC rounds: 1 (the table) .. 4
+    n_hyp: int = 256                    # plane hypotheses per round, 1 .. 1024
+    tol: float = 0.005                  # a pixel within tol of a plane is on it
+    min_plane_fraction: float = 0.1     # a plane is accepted when it holds this share of the round's candidates
+    z_min: float = 0.0                  # candidates: z_min <= |z| <= z_max
+    z_max: float = float("inf")
+    jump_abs: float = 0.01              # neighbours are linked when |za - zb| <= jump_abs + jump_rel * min(za, zb)
+    jump_rel: float = 0.01
+    select: str = "largest"             # "largest" | "center" | "all"
+    min_pixels: int = 6                 # components below this count for nothing
+    anchor: Optional[Sequence] = None   # "center": [V,2] or [2] pixels (column, line); default rint(K02), rint(K12)
+
+    def __post_init__(self):
+        if not 1 <= int(self.max_planes) <= _ISOLATE_MAX_PLANES:
+            raise ValueError(f"max_planes must be 1 .. {_ISOLATE_MAX_PLANES}, got {self.max_planes}")
+        if not 1 <= int(self.n_hyp) <= _ISOLATE_MAX_HYP:
+            raise ValueError(f"n_hyp must be 1 .. {_ISOLATE_MAX_HYP}, got {self.n_hyp}")
+        for name in ("tol", "jump_abs", "jump_rel"):
+            if not (0.0 <= float(getattr(self, name)) < float("inf")):
+                raise ValueError(f"{name} must be finite and non-negative, got {getattr(self, name)}")
+        if not 0.0 <= float(self.min_plane_fraction) <= 1.0:
+            raise ValueError(f"min_plane_fraction must be in [0, 1], got {self.min_plane_fraction}")
+        if not (0.0 <= float(self.z_min) <= float(self.z_max)):
+            raise ValueError(f"0 <= z_min <= z_max is required, got {self.z_min}, {self.z_max}")
+        if self.select not in ISOLATE_SELECT:
+            raise ValueError(f"select must be one of {ISOLATE_SELECT}, got {self.select!r}")
+        if int(self.min_pixels) < 1:
+            raise ValueError(f"min_pixels must be positive, got {self.min_pixels}")
+        if self.anchor is not None and np.asarray(self.anchor).size % 2:
+            raise ValueError("anchor must be [V, 2] or [2] pixels (column, line)")
+
+
+@dataclass
+class ObjectIsolation:
+    """``isolate_objects``: everything on the input's device"""
+    keep: torch.Tensor            # [V,H,W] u8: the object's pixels
+    labels: torch.Tensor          # [V,H,W] i32: the smallest pixel index of the pixel's component, -1 off the candidates
+    sizes: torch.Tensor           # [V,H*W] i32: a component's pixels, at its root pixel
+    planes: torch.Tensor          # [V,max_planes,4] f64: (nx, ny, nz, d), d > 0; NaN for a round that accepted none
+    plane_inliers: torch.Tensor   # [V,max_planes] i32
+    n_planes: torch.Tensor        # [V] i32
+    chosen: torch.Tensor          # [V] i32: the chosen component's root, -1 when none
+    status: torch.Tensor          # [V] i32: ISOLATE_OK / ISOLATE_NO_PLANE / ISOLATE_EMPTY
+
+
+def _plane_dist(pl, x, y, z):
+    return ((pl[..., 0:1] * x + pl[..., 1:2] * y) + pl[..., 2:3] * z) + pl[..., 3:4]
+
+
+def _isolate_frame_numpy(xyz, valid, H, W, seed, cfg: IsolateConfig, anchor):
+    """section OB on one frame's rows (xyz [HW,3] f32, valid [HW] bool) in numpy / scipy, float64 in the contract's order"""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import connected_components
+    HW, nh, tol = H * W, int(cfg.n_hyp), float(cfg.tol)
+    P = xyz.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        absz = np.abs(P[:, 2])
+        cand = valid & (absz >= cfg.z_min) & (absz <= cfg.z_max)
+    pix = np.nonzero(valid)[0]
+    planes = np.full((cfg.max_planes, 4), np.nan)
+    inliers = np.zeros(cfg.max_planes, dtype=np.int32)
+    for r in range(int(cfg.max_planes)):
+        # stage 1: the triples, with the redraw of pixels that are no candidates any more
+        hyp = np.full((nh, 4), np.nan)
+        p0_pix = np.full(nh, -1, dtype=np.int64)
+        if pix.shape[0] >= 3:
+            counter = 3 * nh * r + np.arange(3 * nh, dtype=np.int64)
+            rank = np.full(3 * nh, -1, dtype=np.int64)
+            for t in range(_ISOLATE_TRIES):
+                todo = rank < 0
+                if not todo.any():
+                    break
+                got = frame_hash(seed, counter[todo] + t * 3 * nh * _ISOLATE_MAX_PLANES).astype(np.int64) % pix.shape[0]
+                rank[todo] = np.where(cand[pix[got]], got, -1)
+            rk = rank.reshape(nh, 3)
+            ok = (rk >= 0).all(1) & (rk[:, 0] != rk[:, 1]) & (rk[:, 0] != rk[:, 2]) & (rk[:, 1] != rk[:, 2])
+            tri = P[pix[np.maximum(rk, 0)]]  # [nh, 3 points, 3]
+            e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+            m = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                          e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+            sq = lambda a: (a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]  # noqa: E731
+            with np.errstate(all="ignore"):
+                mm = sq(m)
+                ok &= mm > 1e-12 * (sq(e1) * sq(e2))
+                n = m / np.sqrt(mm)[:, None]
+                d = -((n[:, 0] * tri[:, 0, 0] + n[:, 1] * tri[:, 0, 1]) + n[:, 2] * tri[:, 0, 2])
+            neg = d < 0
+            n, d = np.where(neg[:, None], -n, n), np.where(neg, -d, d)
+            ok &= d > 0
+            hyp[ok] = np.concatenate([n, d[:, None]], 1)[ok]
+            p0_pix[ok] = pix[rk[ok, 0]]
+        # stage 2 and the winner
+        C = P[cand]
+        counts = np.zeros(nh, dtype=np.int64)
+        with np.errstate(invalid="ignore"):
+            for k0 in range(0, nh, 64):
+                h = hyp[k0:k0 + 64]
+                counts[k0:k0 + 64] = (np.abs(_plane_dist(h, C[None, :, 0], C[None, :, 1], C[None, :, 2])) <= tol).sum(1)
+        win = int(np.argmax(counts)) if counts.max(initial=0) > 0 else -1  # (argmax: the lowest k of the largest count)
+        # stage 3: refit and accept
+        plane, n_in = None, 0
+        if win >= 0:
+            with np.errstate(invalid="ignore"):
+                inl = cand & (np.abs(_plane_dist(hyp[win], P[:, 0], P[:, 1], P[:, 2])) <= tol)
+            cnt = int(inl.sum())
+            if cnt >= 3:
+                p0 = P[p0_pix[win]]
+                q = P[inl] - p0
+                s = q.sum(0)
+                mean = p0 + s / np.float64(cnt)
+                nrm = np.linalg.eigh(q.T @ q - np.outer(s, s) / np.float64(cnt))[1][:, 0]
+                nrm = nrm / np.sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2])
+                d = -((nrm[0] * mean[0] + nrm[1] * mean[1]) + nrm[2] * mean[2])
+                if d < 0:
+                    nrm, d = -nrm, -d
+                if d > 0:
+                    fit = np.array([nrm[0], nrm[1], nrm[2], d])
+                    with np.errstate(invalid="ignore"):
+                        n_in = int((cand & (np.abs(_plane_dist(fit, P[:, 0], P[:, 1], P[:, 2])) <= tol)).sum())
+                    if n_in >= 3 and float(n_in) >= float(cfg.min_plane_fraction) * float(cand.sum()):
+                        plane = fit
+        if plane is not None:  # stage 4
+            planes[r], inliers[r] = plane, n_in
+            with np.errstate(invalid="ignore"):
+                cand = cand & (_plane_dist(plane, P[:, 0], P[:, 1], P[:, 2]) > tol)
+    n_planes = int((planes[:, 3] > 0).sum())
+    # stage 5
+    with np.errstate(invalid="ignore"):
+        z, c2 = absz.reshape(H, W), cand.reshape(H, W)
+        lr = c2[:, :-1] & c2[:, 1:] & (np.abs(z[:, :-1] - z[:, 1:]) <= cfg.jump_abs + cfg.jump_rel * np.minimum(z[:, :-1], z[:, 1:]))
+        ud = c2[:-1] & c2[1:] & (np.abs(z[:-1] - z[1:]) <= cfg.jump_abs + cfg.jump_rel * np.minimum(z[:-1], z[1:]))
+    idx = np.arange(HW).reshape(H, W)
+    a, b = np.concatenate([idx[:, :-1][lr], idx[:-1][ud]]), np.concatenate([idx[:, 1:][lr], idx[1:][ud]])
+    _, comp = connected_components(csr_matrix((np.ones(a.shape[0], dtype=np.int8), (a, b)), shape=(HW, HW)), directed=False)
+    order = np.argsort(comp, kind="stable")                      # a component's pixels ascending: its first is the label
+    first = np.r_[True, comp[order][1:] != comp[order][:-1]]
+    root_of_comp = np.zeros(comp.max() + 1, dtype=np.int64)
+    root_of_comp[comp[order][first]] = order[first]
+    labels = np.where(cand, root_of_comp[comp], -1).astype(np.int32)
+    sizes = np.bincount(labels[cand], minlength=HW).astype(np.int32)
+    # stage 6
+    big = sizes >= int(cfg.min_pixels)
+    chosen = -1
+    if big.any():
+        if cfg.select == "center":
+            ax, ay = (min(max(int(v), -16384), 32767) for v in anchor)
+            p = np.nonzero(cand & big[np.maximum(labels, 0)])[0]
+            key = (((p % W - ax) ** 2 + (p // W - ay) ** 2).astype(np.uint64) << np.uint64(32)) | p.astype(np.uint64)
+            chosen = int(labels[p[np.argmin(key)]])
+        else:
+            roots = np.nonzero(big)[0]
+            key = (sizes[roots].astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - roots.astype(np.uint64))
+            chosen = int(roots[np.argmax(key)])
+    if chosen < 0:
+        keep, status = np.zeros(HW, dtype=np.uint8), ISOLATE_EMPTY
+    else:
+        keep = ((cand & big[np.maximum(labels, 0)]) if cfg.select == "all" else labels == chosen).astype(np.uint8)
+        status = ISOLATE_OK if n_planes > 0 else ISOLATE_NO_PLANE
+    return keep, labels, sizes, planes, inliers, n_planes, chosen, status
+
+
+def _isolate_anchor(cfg: IsolateConfig, K: torch.Tensor, V: int) -> np.ndarray:
+    """[V,2] i32 (column, line): the caller's anchor, or the principal point rounded half to even"""
+    if cfg.anchor is None:
+        Kn = K.numpy()
+        a = np.stack([np.rint(Kn[:, 0, 2]), np.rint(Kn[:, 1, 2])], 1)
+    else:
+        a = np.rint(np.asarray(torch.as_tensor(cfg.anchor).cpu() if torch.is_tensor(cfg.anchor) else cfg.anchor, dtype=np.float64))
+        a = np.broadcast_to(a.reshape(-1, 2), (V, 2)) if a.size == 2 else a.reshape(-1, 2)
+        if a.shape[0] != V:
+            raise ValueError(f"{V} frames need {V} anchors, got {a.shape[0]}")
+    return np.clip(a, -16384, 32767).astype(np.int32)
+
+
+def _isolate_checked(depth, K, keep, seeds, depth_scale, flip, cfg: IsolateConfig) -> ObjectIsolation:
+    V, H, W = (int(v) for v in depth.shape)
+    anchor = _isolate_anchor(cfg, K, V)
+    if depth.is_cuda:
+        from . import backend
+        hip = backend.raw()
+        if hip.name != "hip":
+            raise RuntimeError("isolate_objects on GPU tensors needs the HIP library as the operator backend")
+        dev = depth.device
+        rgb = torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev)  # (the rows' colours are not read here)
+        rows, valid, valid_counts = hip.frame_backproject(depth, rgb, K.to(dev, non_blocking=True), keep, depth_scale, flip)
+        got = hip.frame_isolate(rows, valid, valid_counts, seeds, cfg.max_planes, cfg.n_hyp, cfg.tol, cfg.min_plane_fraction, cfg.z_min,
+                                cfg.z_max, cfg.jump_abs, cfg.jump_rel, cfg.select, cfg.min_pixels,
+                                torch.from_numpy(anchor).to(dev, non_blocking=True) if cfg.select == "center" else None)
+        return ObjectIsolation(*(got[f] for f in ("keep", "labels", "sizes", "planes", "plane_inliers", "n_planes", "chosen", "status")))
+    d = depth.numpy()
+    rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, np.zeros((V, H, W, 3), dtype=np.uint8), K.numpy(),
+                                     None if keep is None else keep.numpy(), depth_scale, flip)
+    per = [_isolate_frame_numpy(rows[v * H * W:(v + 1) * H * W, :3], valid[v], H, W, seeds[v], cfg, anchor[v]) for v in range(V)]
+    col = lambda i, dt: torch.from_numpy(np.stack([np.asarray(p[i]) for p in per]).astype(dt)) if V else torch.zeros((0,), dtype=torch.int32)  # noqa: E731
+    return ObjectIsolation(keep=col(0, np.uint8).reshape(V, H, W), labels=col(1, np.int32).reshape(V, H, W), sizes=col(2, np.int32).reshape(V, H * W),
+                           planes=col(3, np.float64).reshape(V, cfg.max_planes, 4), plane_inliers=col(4, np.int32).reshape(V, cfg.max_planes),
+                           n_planes=col(5, np.int32).reshape(V), chosen=col(6, np.int32).reshape(V), status=col(7, np.int32).reshape(V))
+
+
+def isolate_objects(depth, K, depth_scale: float = 1.0, flip: bool = False, keep=None, seed=0,
+                    config: Optional[IsolateConfig] = None) -> ObjectIsolation:
+    """The object of every raw RGB-D frame without a segmenter (include/gpn.h section OB; csrc/isolate.hip): the dominant planes by
+    seeded RANSAC (the table, a wall), what lies on or behind them dropped, the connected components of the rest under a
+    depth-continuity rule, and the object's component chosen (``IsolateConfig.select``).  ``depth`` [V,H,W] (or [H,W]), ``K``, ``keep``,
+    ``depth_scale``, ``flip``, ``seed`` as in ``prepare_frames``.  The result's ``keep`` is what ``prepare_frames(keep=)`` takes; no
+    host read is made.  CPU tensors take the same contract in numpy / scipy."""
+    cfg = IsolateConfig() if config is None else config
+    depth = torch.as_tensor(depth)
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    V = 1 if depth.dim() == 2 else int(depth.shape[0])
+    depth, _, K, keep = _check_frames(depth, torch.zeros((V, H, W, 3) if depth.dim() == 3 else (H, W, 3), dtype=torch.uint8), K, keep)
+    return _isolate_checked(depth, K, keep, _frame_seeds(seed, V), depth_scale, flip, cfg)
+
+
 def prepare_frames(depth, rgb, K, num_points: int = 20000, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
-                   flip: bool = False, hash_bits: int = 32, max_groups: int = 0, sampler: str = "fps") -> PreparedClouds:
+                   flip: bool = False, hash_bits: int = 32, max_groups: int = 0, sampler: str = "fps",
+                   isolate: Optional[IsolateConfig] = None) -> PreparedClouds:
     """V RGB-D frames of one size -> the network's input (include/gpn.h section FR; the reference's ObjIns.get_pc /
     get_downsampled_pc, structure/gapartnet.py:541-627).  ``depth`` [V,H,W] f32 / f64 / u16 (divided by ``depth_scale``), ``rgb``
     [V,H,W,3] u8, ``K`` [V,3,3] or [3,3] (host data), ``keep`` [V,H,W] or None.  Every pixel becomes a row [x y z r g b] (NaN xyz
     where there is no depth); a frame with more than ``presample * num_points`` valid pixels is cut to that many by the seeded
     hash rule (``seed``: one uint32 per frame, or an int s for s, s + 1, ...; ``presample`` 0: no cut), then FPS and the ball
     normalisation of ``prepare_clouds``.  The result's ``source`` is the [V*H*W, 6] rows, its ``sample_rows`` are pixel indices.
-    ``sampler`` "grid": ``prepare_clouds``' octree-cell sampler behind the (unchanged) presample, with the frames' seeds."""
+    ``sampler`` "grid": ``prepare_clouds``' octree-cell sampler behind the (unchanged) presample, with the frames' seeds.
+    ``isolate``: an ``IsolateConfig`` - the frames are back-projected and the object isolated first (``isolate_objects`` with the same
+    ``keep`` and seeds); its mask is the ``keep`` of everything behind, and the result's ``isolation`` holds the
+    ``ObjectIsolation``.  None: nothing changes."""
     depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
-    return _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits, max_groups, sampler)
+    return _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits, max_groups, sampler,
+                                   isolate)
 
 
 def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, depth_scale, flip, hash_bits=32, max_groups=0,
-                            sampler="fps"):
+                            sampler="fps", isolate=None):
     """``prepare_frames`` behind its argument check (``_check_frames``), which the predictor's frame entries run themselves"""
     _check_sampler(sampler)
+    if isolate is not None:
+        # (the isolation's candidates are valid pixels of a back-projection under the caller's keep: its mask lies inside it)
+        iso = _isolate_checked(depth, K, keep, _frame_seeds(seed, int(depth.shape[0])), depth_scale, flip, isolate)
+        prep = _prepare_checked_frames(depth, rgb, K, iso.keep, num_points, presample, seed, depth_scale, flip, hash_bits, max_groups,
+                                       sampler)
+        prep.isolation = iso
+        return prep
     V, H, W = (int(v) for v in depth.shape)
     m, cap = int(num_points), int(presample) * int(num_points)
     if m < 1 or cap < 0:
@@ -465,9 +704,13 @@ class FramePrediction:
     overlay: torch.Tensor           # [H,W,3] u8: the frame's RGB with every box drawn (draw_bbox, structure/utils.py:55-90)
     sample_rows: torch.Tensor       # [m] i64: the sampled pixels (linear indices)
     masks: Optional["MaskPrediction"] = None
+    keep: Optional[torch.Tensor] = None            # with ``isolate``: [H,W] u8, the object's pixels (include/gpn.h section OB)
+    planes: Optional[torch.Tensor] = None          # with ``isolate``: [max_planes,4] f64 (nx, ny, nz, d), NaN where none was accepted
+    isolate_status: Optional[int] = None           # with ``isolate``: ISOLATE_OK / ISOLATE_NO_PLANE / ISOLATE_EMPTY
 
     def to_numpy(self) -> dict:
-        out = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items() if k != "masks"}
+        out = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in self.__dict__.items()
+               if k != "masks" and not (k in ("keep", "planes", "isolate_status") and v is None)}
         if self.masks is not None:
             out.update({"mask_" + f: v for f, v in self.masks.to_numpy().items() if f in MASK_FIELDS or f == "label_votes"})
         return out
@@ -823,21 +1066,33 @@ class PartPredictor:
 
     @torch.no_grad()
     def predict_frames(self, depth, rgb, K, picks: Picks = None, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
-                       flip: bool = False) -> List["FramePrediction"]:
+                       flip: bool = False, isolate: Optional[IsolateConfig] = None) -> List["FramePrediction"]:
         """RGB-D frames in (``prepare_frames``), per frame the parts of EVERY pixel as [H,W] maps, one 9-DoF box per part in the
         camera frame, the boxes' corner pixels and the RGB image with the boxes drawn.  ``flip``: the rows (and so the network's
         input) have y and z negated, as the reference's ``get_pc`` mode 2; boxes are turned back before they are returned and drawn.
         Host reads: 6, those of ``predict`` and no more (7 when ``picks`` is a callable) - ONE for the preparation (counts, status,
         scale), the model's own (voxelisation, proposal stage), post-processing, box selection, ONE for the scenes of the proposals
-        and boxes; ``K`` is host data."""
+        and boxes; ``K`` is host data.  ``isolate``: the object is cut out of the raw frame first (``isolate_objects``); the
+        predictions gain ``keep``, ``planes`` and ``isolate_status``, for ONE more host read (the statuses)."""
         depth, rgb, K, keep = _check_frames(depth, rgb, K, keep)
-        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip, sampler=self.sampler)
-        return self._frame_predictions(self._predict_prepared(prep, picks), rgb, K, flip)
+        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip, sampler=self.sampler,
+                                       isolate=isolate)
+        return self._with_isolation(self._frame_predictions(self._predict_prepared(prep, picks), rgb, K, flip), prep)
+
+    @staticmethod
+    def _with_isolation(frames: List["FramePrediction"], prep: PreparedClouds) -> List["FramePrediction"]:
+        iso = prep.isolation
+        if iso is not None:
+            status = iso.status.cpu().tolist()  # (the one host read isolation adds)
+            for v, f in enumerate(frames):
+                f.keep, f.planes, f.isolate_status = iso.keep[v], iso.planes[v], int(status[v])
+        return frames
 
     @torch.no_grad()
     def predict_frames_with_masks(self, depth, rgb, K, masks: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], picks: Picks = None,
                                   min_points: int = 6, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
-                                  flip: bool = False, features=None, grounder=None) -> List["FramePrediction"]:
+                                  flip: bool = False, features=None, grounder=None,
+                                  isolate: Optional[IsolateConfig] = None) -> List["FramePrediction"]:
         """``predict_with_masks`` on frames: ``masks[v]`` [K_v, H, W] bool / u8 pixel masks (SAM's, or given ones;
         the reference's pixel_mask_to_point_mask), ``labels[v]`` [K_v] part classes.  Flattened, a pixel mask is a mask over the
         frame's rows.  -> ``FramePrediction`` per frame, its fields PER MASK in the caller's order where ``predict_frames`` has them
@@ -869,7 +1124,8 @@ class PartPredictor:
         ask = [v for v, lab in enumerate(labels) if lab is None]
         if ask:
             labels, votes = self._ground_labels(ask, labels, votes, masks, (H, W), V, features, grounder)
-        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip, sampler=self.sampler)
+        prep = _prepare_checked_frames(depth, rgb, K, keep, self.num_points, presample, seed, depth_scale, flip, sampler=self.sampler,
+                                       isolate=isolate)
         mp = self._predict_masks_prepared(prep, flat, labels, picks, min_points)
         for p, vt in zip(mp, votes):
             p.label_votes = vt
@@ -877,12 +1133,13 @@ class PartPredictor:
         unflip = torch.tensor([1.0, -1.0, -1.0] if flip else [1.0, 1.0, 1.0], dtype=torch.float64).to(dev, non_blocking=True)
         boxes = [p.bbox * unflip for p in mp]   # (NaN where not valid: drawn by nobody)
         overlay = draw_overlays(rgb, boxes, K)
-        return [FramePrediction(status=p.status, scale=p.cloud_scale, sem=p.sem.reshape(H, W),
-                                instance=torch.full((H, W), -1, dtype=torch.int64, device=dev),
-                                npcs=torch.zeros((H, W, 3), dtype=torch.float32, device=dev), proposal_scores=p.score,
-                                proposal_classes=p.label, bbox=boxes[v], box_proposal=torch.arange(boxes[v].shape[0], device=dev),
-                                corners_px=project_corners(boxes[v], K[v]), overlay=overlay[v], sample_rows=p.sample_rows, masks=p)
-                for v, p in enumerate(mp)]
+        return self._with_isolation(
+            [FramePrediction(status=p.status, scale=p.cloud_scale, sem=p.sem.reshape(H, W),
+                             instance=torch.full((H, W), -1, dtype=torch.int64, device=dev),
+                             npcs=torch.zeros((H, W, 3), dtype=torch.float32, device=dev), proposal_scores=p.score,
+                             proposal_classes=p.label, bbox=boxes[v], box_proposal=torch.arange(boxes[v].shape[0], device=dev),
+                             corners_px=project_corners(boxes[v], K[v]), overlay=overlay[v], sample_rows=p.sample_rows, masks=p)
+             for v, p in enumerate(mp)], prep)
 
 
 # ---------------------------------------------------------------------------------------------------- files and the command line
@@ -1024,13 +1281,19 @@ def _main_frames(ap, args, model, device) -> int:
     names = [os.path.splitext(os.path.basename(p))[0] for p in args.depth]
     os.makedirs(args.out, exist_ok=True)
     predictor = PartPredictor(model, num_points=args.num_points, sampler=args.sampler)
+    isolate = None
+    if args.isolate:
+        try:
+            isolate = IsolateConfig(max_planes=args.isolate_planes, tol=args.plane_tol, select=args.isolate_select, z_max=args.z_max)
+        except ValueError as e:
+            ap.error(str(e))
     preds: List[Optional[FramePrediction]] = [None] * n
     # (one batch per frame size and depth type)
     for key in sorted({(d.shape, d.dtype.str) for d in depth}):
         ids = [i for i, d in enumerate(depth) if (d.shape, d.dtype.str) == key]
         stack = lambda arrs: torch.from_numpy(np.stack([arrs[i] for i in ids])).to(device)  # noqa: E731
         kw = dict(presample=args.presample, seed=[(args.seed + i) & 0xffffffff for i in ids], keep=None if keep is None else stack(keep),
-                  depth_scale=args.depth_scale, flip=args.flip)
+                  depth_scale=args.depth_scale, flip=args.flip, isolate=isolate)
         K = torch.from_numpy(np.stack([Ks[i] for i in ids]))
         if given is None:
             got = predictor.predict_frames(stack(depth), stack(rgb), K, **kw)
@@ -1048,6 +1311,8 @@ def _main_frames(ap, args, model, device) -> int:
         np.savez(os.path.join(args.out, name + ".npz"), **arrays)
         Image.fromarray(arrays["overlay"]).save(os.path.join(args.out, name + "_overlay.png"), compress_level=1)
         line = f"{name}: {STATUS_NAMES.get(p.status, p.status)}, {p.sem.shape[0]} x {p.sem.shape[1]} pixels"
+        if p.isolate_status is not None:
+            line += f", isolation {ISOLATE_STATUS_NAMES.get(p.isolate_status, p.isolate_status)} ({int(arrays['keep'].sum())} pixels kept)"
         if p.masks is not None:
             line += f"; {p.masks.kept.shape[0]} masks, {int(p.masks.kept.sum())} kept, {int(p.masks.valid.sum())} boxes"
         else:
@@ -1066,6 +1331,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--depth_scale", type=float, default=1.0, help="depth units per metre (1000 for millimetre PNGs)")
     ap.add_argument("--keep_mask", nargs="+", default=None, help="one image per frame: non-zero pixels are kept")
     ap.add_argument("--flip", action="store_true", help="frames: negate y and z of the rows (the reference's get_pc mode 2)")
+    ap.add_argument("--isolate", action="store_true",
+                    help="frames: cut the object out of the raw frame first (planes by RANSAC, connected components); the .npz gains "
+                         "keep, planes and isolate_status")
+    ap.add_argument("--isolate_planes", type=int, default=1, help="--isolate: plane rounds, 1 (the table) .. 4")
+    ap.add_argument("--plane_tol", type=float, default=0.005, help="--isolate: a pixel within this of a plane is on it (depth units)")
+    ap.add_argument("--isolate_select", choices=ISOLATE_SELECT, default="largest", help="--isolate: which component is the object")
+    ap.add_argument("--z_max", type=float, default=float("inf"), help="--isolate: ignore pixels deeper than this")
     ap.add_argument("--presample", type=int, default=4, help="frames: keep at most presample * num_points pixels before FPS (0: all)")
     ap.add_argument("--seed", type=int, default=0, help="frames: seed of the presample (frame i of the command line takes seed + i)")
     ap.add_argument("--out", required=True)

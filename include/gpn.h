@@ -965,6 +965,99 @@ int gpn_cloud_grid_sample(const float* packed, int64_t n_bound, const int32_t* c
                           int m, int hash_bits, int32_t* idx, int32_t* level, void* ws, size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * OB - object isolation: the `keep` mask of gpn_frame_backproject from the raw frame itself, by classical geometry - seeded RANSAC
+ * planes (the table, a wall), the cut at them, connected components of what is left in image space, the object's component.  The
+ * reference takes this mask from Grounded-SAM (seg_obj -> obj_mask, structure/gapartnet.py:742-749), which is out of scope here.
+ * The rules of section FR hold: a batch of V frames of one size H x W (V <= 65535; here also H, W <= 16384); no host read between
+ * the launches; no float atomics; integer atomics only where their order cannot matter (counters, min / max by integer compare);
+ * every output is bit-reproducible and independent of what else is in the batch.  The library is built with -ffp-contract=off:
+ * every float64 expression below is evaluated as written, one rounding per operation, so numpy gives the same bits.
+ * Inputs: rows [V*H*W, 6] f32, valid [V,H,W] u8 and valid_counts [V] i32 of gpn_frame_backproject; pix [V, H*W] i32 of
+ * gpn_frame_select with cap == 0 (the valid pixels, ascending); seeds [V] u32.  (x, y, z) of a pixel are its row's first three
+ * floats cast to float64.  flip frames work unchanged: the camera is at the origin either way, and "depth" means |z|.
+ * A plane is (nx, ny, nz, d) f64 with |n| = 1 and d > 0 - the camera on the positive side; dist(p) = ((nx*x + ny*y) + nz*z) + d.
+ * gpn_frame_candidates: cand [V,H,W] u8 = valid && z_min <= |z| <= z_max (z_min >= 0; z_max may be +inf).  cand is the state of
+ *   the rounds: gpn_frame_plane_cut clears bytes of it.
+ * gpn_frame_plane_hypotheses (stage 1): hyp [V, n_hyp, 4] f64, 1 <= n_hyp <= GPN_ISOLATE_MAX_HYP; hyp_pix [V, n_hyp] i32 = the
+ *   pixel of the hypothesis' first point p0, -1 where degenerate.  Point j = 0, 1, 2 of hypothesis k in round r has the counter
+ *   c = 3 * n_hyp * r + 3 k + j.  DECISION: a round draws from pix (all valid pixels) and REDRAWS a pixel that is no candidate any
+ *   more, rather than compacting the candidates again: try t = 0 .. GPN_ISOLATE_TRIES - 1 takes the rank
+ *   hash(seed_v, c + t * 3 * n_hyp * GPN_ISOLATE_MAX_PLANES) mod valid_counts[v] (uint32 arithmetic that wraps; hash = the
+ *   mix(mix(i + seed * 0x9E3779B9) ^ seed) of section FR), and the first try whose pixel pix[v, rank] is a candidate is taken;
+ *   none: the hypothesis is degenerate.  The tries' counters lie beyond every round's first tries.  With cand == valid the first
+ *   try always hits.  With p0, p1, p2 the three points, e1 = p1 - p0, e2 = p2 - p0:
+ *     m = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x);  mm = (mx*mx + my*my) + mz*mz;  |e|^2 summed the same way
+ *     n = m / sqrt(mm) (each component divided);  d = -((nx*p0x + ny*p0y) + nz*p0z);  d < 0: n = -n, d = -d
+ *   Degenerate (all four NaN, scores 0): two of the three ranks coincide; not mm > 1e-12 * (|e1|^2 * |e2|^2); d == 0;
+ *   valid_counts[v] < 3; a point with no candidate in GPN_ISOLATE_TRIES tries.
+ * gpn_frame_plane_score (stage 2): counts [V, n_hyp] i32 = the number of candidates with |dist(p)| <= tol (tol >= 0, finite, in
+ *   the rows' units); zeroed by the call.  variant 0: a workgroup per 1024-pixel chunk, the chunk's candidates in LDS as float64, a
+ *   thread per hypothesis walking them, one integer atomicAdd per hypothesis and workgroup; variant 1: pixels in registers, ballot
+ *   and popcount per hypothesis (kept for tools/isolate_bench.py).  The counts are the same.
+ * gpn_frame_plane_winner: winner [V] i32 = the k of the largest count, ties to the lowest k; -1 when every count is 0.
+ * gpn_frame_plane_refit (stage 3): one least-squares refit on the winner's inliers (candidates with |dist| <= tol under hyp[v,
+ *   winner]): with q = p - p0 (p0 = the row of hyp_pix[v, winner]) the sums s = sum q, Q = sum q q^T and the count n, as per-chunk
+ *   partials in the workspace (inside a chunk: each thread its 4 pixels in ascending order, a shuffle tree per wave, the waves in
+ *   order) added up in chunk order; mean = p0 + s / n; C = Q - s s^T / n (C_ab = Q_ab - s_a * s_b / n); the plane's normal is the
+ *   singular vector of C's smallest singular value (svd3, pose_math.h), normalised again; d = -((nx*meanx + ny*meany) + nz*meanz),
+ *   oriented as in stage 1.  The refit's own inliers i (candidates with |dist| <= tol under it) are counted, and the plane is
+ *   ACCEPTED when i >= 3 and (double)i >= min_plane_fraction * (double)(the frame's candidates) (0 <= min_plane_fraction <= 1).
+ *   planes [V, max_planes, 4] f64: entry `round` = the plane, NaN when not accepted (no winner, fewer than 3 inliers, d == 0
+ *   included); plane_inliers [V, max_planes] i32 = i or 0; n_planes [V] i32 = the accepted rounds so far (round 0 sets it).
+ *   1 <= max_planes <= GPN_ISOLATE_MAX_PLANES, 0 <= round < max_planes.
+ * gpn_frame_plane_cut (stage 4): under an accepted planes[v, round] a candidate stays one iff dist(p) > tol - strictly on the
+ *   camera's side and off the plane; the table, the wall behind the object and what the sensor sees "through" them go.  A round
+ *   that was not accepted leaves cand untouched.  The host loops stages 1 - 4 over the rounds; nothing is read back.
+ * gpn_frame_components (stage 5): connected components of the candidates under 4-connectivity; two neighbours are linked iff both
+ *   are candidates and |za - zb| <= jump_abs + jump_rel * min(za, zb), z = |rows.z| in float64 - flying pixels at depth edges fall
+ *   apart into crumbs.  labels [V,H,W] i32 = the SMALLEST linear pixel index of the pixel's component, -1 for a non-candidate - a
+ *   unique result; sizes [V, H*W] i32 = the component's pixels at its root (label) pixel, 0 elsewhere; n_components [V] i32 = the
+ *   components of at least min_pixels (>= 1) pixels.  How: union-find with the parent array in labels.  16 x 16 tiles in LDS, the
+ *   links across tile borders by atomicMin on the global array, then every pixel takes its root.  A root only ever takes a smaller
+ *   parent, parent[i] <= i holds at every moment, so every find walk ends by construction; no workgroup waits for another (no grid
+ *   barrier, no cooperative launch, no flag).
+ * gpn_frame_component_select (stage 6): select = GPN_ISOLATE_SELECT_LARGEST: the component with the most pixels, ties to the
+ *   smallest root; _CENTER: the component that holds the candidate pixel nearest the anchor (anchor [V,2] i32 = column, line; each
+ *   clamped to [-16384, 32767]) by the integer squared pixel distance, ties to the smallest pixel index; _ALL: every component.
+ *   DECISION: under all three rules only components of at least min_pixels pixels count (the reference's "magic number" 6 for a
+ *   usable mask, structure/gapartnet.py:635), so a frame of crumbs is EMPTY under "largest" too.  keep [V,H,W] u8; chosen [V] i32
+ *   = the root (_ALL: the largest's), -1 when none; status [V] i32 = GPN_ISOLATE_EMPTY (no component qualifies, keep all zero),
+ *   else GPN_ISOLATE_NO_PLANE (n_planes[v] == 0: components are selected all the same), else GPN_ISOLATE_OK.
+ * Errors (GPN_ERR_ARG / GPN_ERR_WS, nothing launched): sizes or parameters outside the ranges above, a null pointer with V > 0,
+ * a workspace smaller than the _ws_bytes of the call.  V == 0 returns GPN_OK.
+ * Out of scope: learned segmentation, scenes of several objects beyond _ALL, temporal smoothing.
+ * ================================================================================================ */
+#define GPN_ISOLATE_OK 0
+#define GPN_ISOLATE_NO_PLANE 1
+#define GPN_ISOLATE_EMPTY 2
+#define GPN_ISOLATE_SELECT_LARGEST 0
+#define GPN_ISOLATE_SELECT_CENTER 1
+#define GPN_ISOLATE_SELECT_ALL 2
+#define GPN_ISOLATE_MAX_PLANES 4
+#define GPN_ISOLATE_MAX_HYP 1024
+#define GPN_ISOLATE_TRIES 8
+int gpn_frame_candidates(const float* rows, const uint8_t* valid, int V, int H, int W, double z_min, double z_max, uint8_t* cand,
+                         gpn_stream_t stream);
+int gpn_frame_plane_hypotheses(const float* rows, const uint8_t* cand, const int32_t* pix, const int32_t* valid_counts,
+                               const uint32_t* seeds, int V, int H, int W, int n_hyp, int round, double* hyp, int32_t* hyp_pix,
+                               gpn_stream_t stream);
+int gpn_frame_plane_score(const float* rows, const uint8_t* cand, const double* hyp, int V, int H, int W, int n_hyp, double tol,
+                          int variant, int32_t* counts, gpn_stream_t stream);
+int gpn_frame_plane_winner(const int32_t* counts, int V, int n_hyp, int32_t* winner, gpn_stream_t stream);
+size_t gpn_frame_plane_refit_ws_bytes(int V, int H, int W);
+int gpn_frame_plane_refit(const float* rows, const uint8_t* cand, const double* hyp, const int32_t* hyp_pix, const int32_t* winner,
+                          int V, int H, int W, int n_hyp, double tol, double min_plane_fraction, int round, int max_planes,
+                          double* planes, int32_t* plane_inliers, int32_t* n_planes, void* ws, size_t ws_bytes, gpn_stream_t stream);
+int gpn_frame_plane_cut(const float* rows, const double* planes, int V, int H, int W, int max_planes, int round, double tol,
+                        uint8_t* cand, gpn_stream_t stream);
+int gpn_frame_components(const float* rows, const uint8_t* cand, int V, int H, int W, double jump_abs, double jump_rel, int min_pixels,
+                         int32_t* labels, int32_t* sizes, int32_t* n_components, gpn_stream_t stream);
+size_t gpn_frame_component_select_ws_bytes(int V);
+int gpn_frame_component_select(const int32_t* labels, const int32_t* sizes, const int32_t* n_planes, const int32_t* anchor, int V,
+                               int H, int W, int select, int min_pixels, uint8_t* keep, int32_t* chosen, int32_t* status, void* ws,
+                               size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * RD - articulated assets -> training views (the reference's dataset/render_tools/render.py without SAPIEN): z-depth, the winning
  * triangle, link labels, the NPCS map and a flat-shaded RGB image for a batch of V views of one size H x W (H, W <= 16384, V <=
  * 65535).  Views may show different assets.  No host read between the launches; no float atomics; every pixel is stored once, so
