@@ -2060,6 +2060,125 @@ def joint_from_rigid(rotation, translation, norm, joint_type="revolute"):
     return axis, pivot, angle
 
 
+# ---------------------------------------------------------------------------------------------------- AR (articulation)
+PARTS_MAX = 64
+
+
+def _part_maps(inst, valid, what):
+    """inst [V,H,W] i32 / i64 (FramePrediction.instance is i64) and valid [V,H,W] u8 / bool -> contiguous i32 / u8"""
+    V, H, W = _frame_dims(inst)
+    if inst.dtype != torch.int32:
+        if inst.dtype not in (torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise _C.GpnError(f"{what}: an instance map is an integer tensor, got {inst.dtype}")
+        # (every value outside 0 .. 63 belongs to no part; a plain cast of an int64 would wrap, and so would -1 in an unsigned clamp)
+        inst = inst.to(torch.int64).clamp(-1, PARTS_MAX).to(torch.int32)
+    if tuple(valid.shape) != (V, H, W):
+        raise _C.GpnError(f"{what}: valid must be [V,H,W] like the instance map")
+    return inst.contiguous(), _c(valid, torch.uint8), V, H, W
+
+
+def _part_counts(n, V, dev, what):
+    """[V] part counts (a tensor on the device, or host ints) -> i32 tensor on the device"""
+    if torch.is_tensor(n):
+        n = _c(n.to(dev, non_blocking=True), torch.int32)
+    else:
+        n = torch.tensor([int(x) for x in n], dtype=torch.int32).to(dev, non_blocking=True)
+    if n.numel() != V:
+        raise _C.GpnError(f"{what}: one part count per frame")
+    return n
+
+
+def _part_width(P, what):
+    P = int(P)
+    if not 0 <= P <= PARTS_MAX:
+        raise _C.GpnError(f"{what}: a table width is 0 .. {PARTS_MAX}, got {P}")
+    return P
+
+
+def _part_classes(cls, V, P, dev, what):
+    """ragged class lists (a sequence of V tensors / lists) or a [V,P] tensor -> [V,P] i32 on the device, -1 beyond a list's end"""
+    if cls is None:
+        return None
+    if torch.is_tensor(cls):
+        if tuple(cls.shape) != (V, P):
+            raise _C.GpnError(f"{what}: a class table is [V,P]")
+        return _c(cls.to(dev, non_blocking=True), torch.int32)
+    if len(cls) != V:
+        raise _C.GpnError(f"{what}: one class list per frame")
+    table = torch.full((V, P), -1, dtype=torch.int32, device=dev)
+    for v, c in enumerate(cls):  # (a list that lives on the device is padded there: no host read)
+        c = torch.as_tensor(c).reshape(-1)
+        if c.shape[0] > P:
+            raise _C.GpnError(f"{what}: frame {v} has {c.shape[0]} classes, the table is {P} wide")
+        if c.shape[0]:
+            table[v, :c.shape[0]] = c.to(dev, non_blocking=True).to(torch.int32)
+    return table
+
+
+def parts_overlap(inst_a, valid_a, n_a, inst_b, valid_b, n_b, PA, PB):
+    """the contingency table of two instance maps (include/gpn.h section AR): inst [V,H,W] i32 / i64, valid [V,H,W] u8 / bool,
+    n [V] part counts, PA / PB the table widths -> (inter [V,PA,PB], area_a [V,PA], area_b [V,PB]) i32 on the device"""
+    dev = _dev(inst_a, valid_a, inst_b, valid_b)
+    inst_a, valid_a, V, H, W = _part_maps(inst_a, valid_a, "parts_overlap")
+    inst_b, valid_b, Vb, Hb, Wb = _part_maps(inst_b, valid_b, "parts_overlap")
+    if (Vb, Hb, Wb) != (V, H, W):
+        raise _C.GpnError("parts_overlap: both frames of a pair have one size")
+    PA, PB = _part_width(PA, "parts_overlap"), _part_width(PB, "parts_overlap")
+    n_a, n_b = _part_counts(n_a, V, dev, "parts_overlap"), _part_counts(n_b, V, dev, "parts_overlap")
+    inter = torch.empty((V, PA, PB), dtype=torch.int32, device=dev)
+    area_a = torch.empty((V, PA), dtype=torch.int32, device=dev)
+    area_b = torch.empty((V, PB), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_parts_overlap(ptr(inst_a), ptr(valid_a), ptr(n_a), ptr(inst_b), ptr(valid_b), ptr(n_b), i32(V), i32(H), i32(W),
+                                     i32(PA), i32(PB), ptr(inter), ptr(area_a), ptr(area_b), _stream()), "gpn_parts_overlap")
+    return inter, area_a, area_b
+
+
+def parts_match(inter, area_a, area_b, n_a, n_b, cls_a=None, cls_b=None, min_iou=0.1):
+    """greedy one-to-one matching by exact mask IoU (section AR): the tables of parts_overlap, n [V] part counts, cls = ragged class
+    lists or [V,P] tables (None: all classes equal) -> dict(match_ab [V,PA], match_ba [V,PB], n_matched [V], inter [V,PA],
+    union [V,PA]) i32 on the device"""
+    dev = _dev(inter, area_a, area_b)
+    if inter.dim() != 3:
+        raise _C.GpnError("parts_match: inter is [V,PA,PB]")
+    V, PA, PB = (int(v) for v in inter.shape)
+    _part_width(PA, "parts_match"), _part_width(PB, "parts_match")
+    inter, area_a, area_b = (_c(t, torch.int32) for t in (inter, area_a, area_b))
+    if tuple(area_a.shape) != (V, PA) or tuple(area_b.shape) != (V, PB):
+        raise _C.GpnError("parts_match: area_a [V,PA] and area_b [V,PB]")
+    n_a, n_b = _part_counts(n_a, V, dev, "parts_match"), _part_counts(n_b, V, dev, "parts_match")
+    cls_a, cls_b = _part_classes(cls_a, V, PA, dev, "parts_match"), _part_classes(cls_b, V, PB, dev, "parts_match")
+    out = dict(match_ab=torch.empty((V, PA), dtype=torch.int32, device=dev), match_ba=torch.empty((V, PB), dtype=torch.int32, device=dev),
+               n_matched=torch.empty((V,), dtype=torch.int32, device=dev), inter=torch.empty((V, PA), dtype=torch.int32, device=dev),
+               union=torch.empty((V, PA), dtype=torch.int32, device=dev))
+    check(_C.lib().gpn_parts_match(ptr(inter), ptr(area_a), ptr(area_b), ptr(n_a), ptr(n_b), ptr(cls_a), ptr(cls_b), _dbl(float(min_iou)),
+                                   i32(V), i32(PA), i32(PB), ptr(out["match_ab"]), ptr(out["match_ba"]), ptr(out["n_matched"]),
+                                   ptr(out["inter"]), ptr(out["union"]), _stream()), "gpn_parts_match")
+    return out
+
+
+def parts_gather(rows, inst, valid, n_parts, seg_start, n_total, out=None):
+    """the matched parts' pixels as ragged clouds (section AR): rows [V*H*W,6] f32 of frame_backproject, inst / valid [V,H,W],
+    n_parts [V], seg_start [V,P] i64 (negative: drop the part) -> pc [n_total,3] f64; rows no segment covers are not written
+    (``out``: write into this tensor)"""
+    dev = _dev(rows, inst, valid)
+    inst, valid, V, H, W = _part_maps(inst, valid, "parts_gather")
+    rows = _c(rows, torch.float32)
+    if rows.numel() != V * H * W * 6 or seg_start.dim() != 2 or seg_start.shape[0] != V:
+        raise _C.GpnError("parts_gather: one row per pixel and seg_start [V,P]")
+    P = _part_width(seg_start.shape[1], "parts_gather")
+    seg_start = _c(seg_start.to(dev, non_blocking=True), torch.int64)
+    n_parts = _part_counts(n_parts, V, dev, "parts_gather")
+    n_total = int(n_total)
+    pc = torch.empty((n_total, 3), dtype=torch.float64, device=dev) if out is None else out
+    if pc.dtype != torch.float64 or tuple(pc.shape) != (n_total, 3) or not pc.is_contiguous() or pc.device != dev:
+        raise _C.GpnError("parts_gather: out must be a contiguous [n_total,3] float64 tensor on the frames' device")
+    L = _C.lib()
+    ws = _ws(L.gpn_parts_gather_ws_bytes(i32(V), i32(H), i32(W), i32(P)), dev)
+    check(L.gpn_parts_gather(ptr(rows), ptr(inst), ptr(valid), ptr(n_parts), ptr(seg_start), i32(V), i32(H), i32(W), i32(P), i64(n_total),
+                             ptr(pc), ptr(ws), szt(ws.numel()), _stream()), "gpn_parts_gather")
+    return pc
+
+
 # ---------------------------------------------------------------------------------------------------- PE (pose evaluation)
 def pose_gt_fit(xyz, npcs, slot, scene_offsets, W):
     """xyz, npcs [N,3] f32, slot [N] i32 (scene * W + instance id, negative = none), scene_offsets [S+1] i64 -> dict per slot

@@ -266,10 +266,28 @@ def estimate_joints(pc1s: Sequence[torch.Tensor], pc2s: Sequence[torch.Tensor], 
     B = len(pc1s)
     if B == 0 or len(pc2s) != B:
         raise ValueError("estimate_joints needs as many first as second observations, at least one")
+    if joint_type not in ("revolute", "prismatic"):  # (before any work: the concatenation below is a device copy)
+        raise ValueError(f"joint_type is 'revolute' or 'prismatic', got {joint_type!r}")
+    f64 = torch.float64
+    sizes1, sizes2 = [int(p.shape[0]) for p in pc1s], [int(p.shape[0]) for p in pc2s]
+    return estimate_joints_packed(torch.cat([p.to(f64) for p in pc1s]), torch.cat([p.to(f64) for p in pc2s]), sizes1, sizes2,
+                                  sample_number, picks, ransac_picks, joint_type, max_iterations, tolerance, w)
+
+
+@torch.no_grad()
+def estimate_joints_packed(pc1: torch.Tensor, pc2: torch.Tensor, sizes1: Sequence[int], sizes2: Sequence[int],
+                           sample_number: int = 500, picks=None, ransac_picks: Optional[torch.Tensor] = None,
+                           joint_type: str = "revolute", max_iterations: int = 100, tolerance: float = 1e-3,
+                           w: float = 0.0) -> JointEstimate:
+    """``estimate_joints`` on clouds that are already concatenated: ``pc1`` [sum sizes1, 3], ``pc2`` [sum sizes2, 3] f64, pair b =
+    the next ``sizes1[b]`` / ``sizes2[b]`` rows (host ints) - the layout ``gpn_joint_sample`` reads and ``gpn_parts_gather`` writes."""
+    B = len(sizes1)
+    if B == 0 or len(sizes2) != B:
+        raise ValueError("estimate_joints needs as many first as second observations, at least one")
     if joint_type not in ("revolute", "prismatic"):
         raise ValueError(f"joint_type is 'revolute' or 'prismatic', got {joint_type!r}")
-    dev, f64 = pc1s[0].device, torch.float64
-    sizes1, sizes2 = [int(p.shape[0]) for p in pc1s], [int(p.shape[0]) for p in pc2s]
+    dev = pc1.device
+    sizes1, sizes2 = [int(n) for n in sizes1], [int(n) for n in sizes2]
     if picks is None:
         picks = draw_joint_picks(sizes1, sizes2, sample_number)
     picks1, picks2, k1, k2 = picks
@@ -277,11 +295,11 @@ def estimate_joints(pc1s: Sequence[torch.Tensor], pc2s: Sequence[torch.Tensor], 
     if dev.type == "cuda":
         hip = _need_hip("estimate_joints")
         off = [torch.tensor(np.concatenate([[0], np.cumsum(sz)]), dtype=torch.int64).to(dev, non_blocking=True) for sz in (sizes1, sizes2)]
-        X, Y, norm = hip.joint_sample(torch.cat([p.to(f64) for p in pc1s]), torch.cat([p.to(f64) for p in pc2s]), off[0], off[1],
+        X, Y, norm = hip.joint_sample(pc1, pc2, off[0], off[1],
                                       picks1.to(dev, non_blocking=True), picks2.to(dev, non_blocking=True),
                                       k1.to(dev, non_blocking=True), k2.to(dev, non_blocking=True))
     else:
-        X, Y, norm = _joint_sample_torch(pc1s, pc2s, picks1, picks2, k1, k2)
+        X, Y, norm = _joint_sample_torch(torch.split(pc1, sizes1), torch.split(pc2, sizes2), picks1, picks2, k1, k2)
     reg = cpd_rigid_batched(X, Y, k1, k2, max_iterations, tolerance, w)
     # ---- the RANSAC leg: rows 0 .. min(k1, k2) of every pair as a ragged batch ----
     # (a pair with an empty observation enters as one padded row: a single-point proposal has no pose, so its leg is NaN, as the

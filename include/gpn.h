@@ -1216,6 +1216,52 @@ int gpn_joint_from_rigid(const double* rotation, const double* translation, cons
                          double* axis, double* pivot, double* angle, gpn_stream_t stream);
 
 /* ================================================================================================
+ * AR - articulation from two frames: the parts of frame A associated with the parts of frame B, and the matched parts' pixels cut
+ * out as the ragged clouds gpn_joint_sample reads - what lies between section FR's per-pixel instance maps and section JE, which
+ * takes ONE part and asks for its points ("only part, please segment first", structure/gapartnet.py:829).  The reference has no
+ * counterpart.  A batch of V frame pairs of one size H x W (V <= 65535, H and W <= 16384), at most GPN_PARTS_MAX parts a frame.
+ * No host read inside an entry point; no float atomics; integer atomics only on histograms, whose results do not depend on their
+ * order: every output is bit-reproducible and a frame pair's result does not depend on the rest of the batch.  V == 0 is a valid
+ * call that launches nothing, and so is gpn_parts_overlap with both table widths 0 and gpn_parts_gather with P == 0 or n_total == 0;
+ * a single width of 0 is valid too (the tables of that side are empty; gpn_parts_match still writes n_matched = 0).
+ * MEMBERSHIP, the rule of all three entry points: pixel q of frame v belongs to part p iff valid[v,q] != 0 and inst[v,q] == p with
+ *   0 <= p < n_parts[v].  Any other value of inst (-1, a value at or above n_parts[v], a large negative one) belongs to no part.
+ *   inst [V,H,W] i32; valid [V,H,W] u8 as gpn_frame_backproject writes it; n_parts [V] i32 on the device (a count above the table
+ *   width is read as the table width).
+ * gpn_parts_overlap: inter [V,PA,PB] i32 = the pixels that belong to part i in frame A and to part j in frame B; area_a [V,PA],
+ *   area_b [V,PB] i32 = the parts' pixels.  PA, PB <= GPN_PARTS_MAX are the table widths; entries at or beyond the live counts
+ *   are written as 0.  How: a workgroup per chunk of 1024 pixels (the chunk of section FR) fills a PA x PB histogram in LDS by
+ *   integer atomics - a wave first groups its lanes by key with ballots and adds each group's popcount once, since the maps are
+ *   piecewise constant - and flushes the non-zero bins by global integer adds.
+ * gpn_parts_match: GREEDY one-to-one matching by 2D mask IoU, exact.  cls_a [V,PA], cls_b [V,PB] i32 (either NULL: all classes
+ *   equal).  union = area_a[i] + area_b[j] - inter[i,j]; a pair (i, j) is ELIGIBLE iff its classes are equal, inter > 0 and
+ *   (double)inter >= min_iou * (double)union (one float64 product and one comparison).  Repeatedly the eligible pair of an
+ *   unmatched i and an unmatched j with the largest IoU is taken, until none is left.  IoUs are compared exactly, by the 64-bit
+ *   cross products inter1 * union2 and inter2 * union1 (below 2^57 under the frame limits); ties go to the smaller i, then the
+ *   smaller j.  DECISION: greedy, not the optimal (Hungarian) assignment - it is the rule this project's AP matching uses, it is
+ *   a total order, so the result is unique, and it needs no floating-point cost.  Outputs: match_ab [V,PA] i32 = j or -1,
+ *   match_ba [V,PB] i32 = i or -1, n_matched [V] i32, m_inter, m_union [V,PA] i32 (0 where unmatched).  One workgroup a frame
+ *   pair: at most 64 rounds of an arg-max over at most 4096 entries held in LDS.
+ * gpn_parts_gather: one side's clouds.  rows [V*H*W,6] f32 of gpn_frame_backproject; seg_start [V,P] i64 = the first output row of
+ *   the part's segment, or negative to drop the part.  pc [n_total,3] f64: the member pixels of part p of frame v go to rows
+ *   seg_start[v,p] + 0, 1, 2, ... in ascending pixel order, xyz cast f32 -> f64 (exact).  Rows no segment covers are not written;
+ *   a row at or beyond n_total is not written either.  Segment sizes are the areas of gpn_parts_overlap; overlapping segments are
+ *   the caller's error and are not detected.  How: a stable multi-way partition - per-chunk per-part counts, one scan over the
+ *   chunks per (frame, part), stores with the in-chunk rank of every pixel among the earlier pixels of its own part (ballots over
+ *   equal keys inside a wave, LDS counters added in order across the chunk).  Workspace: gpn_parts_gather_ws_bytes.
+ * ================================================================================================ */
+#define GPN_PARTS_MAX 64
+int gpn_parts_overlap(const int32_t* inst_a, const uint8_t* valid_a, const int32_t* n_a, const int32_t* inst_b,
+                      const uint8_t* valid_b, const int32_t* n_b, int V, int H, int W, int PA, int PB, int32_t* inter,
+                      int32_t* area_a, int32_t* area_b, gpn_stream_t stream);
+int gpn_parts_match(const int32_t* inter, const int32_t* area_a, const int32_t* area_b, const int32_t* n_a, const int32_t* n_b,
+                    const int32_t* cls_a, const int32_t* cls_b, double min_iou, int V, int PA, int PB, int32_t* match_ab,
+                    int32_t* match_ba, int32_t* n_matched, int32_t* m_inter, int32_t* m_union, gpn_stream_t stream);
+size_t gpn_parts_gather_ws_bytes(int V, int H, int W, int P);
+int gpn_parts_gather(const float* rows, const int32_t* inst, const uint8_t* valid, const int32_t* n_parts, const int64_t* seg_start,
+                     int V, int H, int W, int P, int64_t n_total, double* pc, void* ws, size_t ws_bytes, gpn_stream_t stream);
+
+/* ================================================================================================
  * PE - pose evaluation: is an estimated part pose right?  The ground-truth pose of every instance, the exact IoU of two oriented
  * boxes, and the errors of matched (prediction, ground truth) pairs under the part's symmetry group: what the GAPartNet paper
  * reports for its second task (R_e, T_e, S_e, 3D IoU).  The reference has no counterpart (on_test_epoch_end ends at a
