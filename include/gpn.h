@@ -314,7 +314,10 @@ int gpn_scatter_rows_csr(const float* dout, const int32_t* order, const int32_t*
  *          full model has no BatchNorm launch left but the proposal networks' first one (network/backbone.py:40-49).
  * backward: slots[].grad of the final slot holds d(loss)/d(output); slots[].grad_state must be 0 everywhere except
  *          slots that already hold a gradient (1).  Gradients of multiply-consumed slots are summed in program order
- *          (reverse), so results are deterministic.  need_input_grad = 0 skips d/d(slot 0). */
+ *          (reverse), so results are deterministic.  need_input_grad = 0 skips d/d(slot 0).
+ * errors:  every pass validates ALL its tables, then its workspace size, before its first launch: GPN_ERR_ARG / GPN_ERR_WS leave
+ *          nothing enqueued.  A BatchNorm over running statistics (training == 0 or GPN_NET_INFERENCE) needs weight, bias,
+ *          running_mean and running_var, whether it is applied by a conv launch or by its own. */
 typedef struct gpn_net_slot {
   float* data;
   float* grad;

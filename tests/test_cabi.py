@@ -155,3 +155,191 @@ def test_executor_rejects_malformed_programs_without_touching_the_device(lib):
     bad["kind"] = 9
     assert run(bad) == 1 and b"unknown op" in lib.gpn_last_error()
     assert lib.gpn_net_forward(None, 1, None, 0, None, 0, None, 0, None, 0, 1, None, ctypes.c_size_t(0), None) == 1
+
+
+# ---- the executor validates a WHOLE pass before its first launch (csrc/net_plan.h) ------------------------------------------------
+# Every call below passes ws = NULL / ws_bytes = 0: a program that slips through validation ends in GPN_ERR_WS (2), never in a
+# launch.  Every pointer in the tables is a fake that must never be dereferenced.
+FAKE = 0x1000
+ERR_ARG, ERR_WS = 1, 2
+INFERENCE = 2  # GPN_NET_INFERENCE
+
+
+def _vp(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def _net_tables(program, rows=100, C=16):
+    """ops, slots, rulebooks, convs, bns of a small program over slots of `rows` x C: "conv_bn", "residual"
+    (CONV-BN-CONV-BN, the last one adding slot 0) or "concat" (CONV-BN-CONCAT-CONV-BN)"""
+    import numpy as np
+    from gapartnet_amd.network import net_exec as NX
+    CONV, BN, CAT, RELU = NX.OP_CONV, NX.OP_BN, NX.OP_CONCAT, NX.FLAG_RELU
+    op_list, channels, conv_shapes = {
+        "conv_bn": ([(CONV, 0, -1, 1, 0, 0, 0, 0), (BN, 1, -1, 2, -1, 0, RELU, 0)], [C, C, C], [(C, C)]),
+        "residual": ([(CONV, 0, -1, 1, 0, 0, 0, 0), (BN, 1, -1, 2, -1, 0, RELU, 0), (CONV, 2, -1, 3, 0, 1, 0, 0),
+                      (BN, 3, 0, 4, -1, 1, RELU, 0)], [C] * 5, [(C, C), (C, C)]),
+        "concat": ([(CONV, 0, -1, 1, 0, 0, 0, 0), (BN, 1, -1, 2, -1, 0, RELU, 0), (CAT, 0, 2, 3, -1, -1, 0, 0),
+                    (CONV, 3, -1, 4, 0, 1, 0, 0), (BN, 4, -1, 5, -1, 1, RELU, 0)], [C, C, C, 2 * C, C, C], [(C, C), (2 * C, C)]),
+    }[program]
+    ops = np.zeros(len(op_list), NX.OP_DT)
+    for i, op in enumerate(op_list):
+        ops[i] = op
+    slots = np.zeros(len(channels), NX.SLOT_DT)
+    slots["rows"], slots["channels"], slots["data"], slots["grad"] = rows, channels, FAKE, FAKE
+    rbs = np.zeros(1, NX.RB_DT)
+    rbs["n_src"], rbs["n_dst"], rbs["K"] = rows, rows, 27
+    for f in ("nbr", "nbr_t", "pair_src", "pair_dst", "tile_off"):
+        rbs[f] = FAKE
+    convs = np.zeros(len(conv_shapes), NX.CONV_DT)
+    convs["cin"], convs["cout"] = [c[0] for c in conv_shapes], [c[1] for c in conv_shapes]
+    convs["W"], convs["dW"] = FAKE, FAKE
+    bns = np.zeros(sum(op[0] == BN for op in op_list), NX.BN_DT)
+    for f in ("weight", "bias", "running_mean", "running_var", "save_mean", "save_invstd", "dweight", "dbias"):
+        bns[f] = FAKE
+    bns["C"], bns["eps"], bns["momentum"] = C, 1e-4, 0.1
+    return ops, slots, rbs, convs, bns
+
+
+def _net_forward(lib, ops, slots, rbs, convs, bns, mode, second=None):
+    """gpn_net_forward, or gpn_net_forward_pair with `second` = (slots, convs, bns) of the second network; no workspace"""
+    lib.gpn_last_error.restype = ctypes.c_char_p
+    n = (len(ops), len(slots), len(rbs), len(convs), len(bns))
+    if second is None:
+        rc = lib.gpn_net_forward(_vp(ops), n[0], _vp(slots), n[1], _vp(rbs), n[2], _vp(convs), n[3], _vp(bns), n[4], mode, None,
+                                 ctypes.c_size_t(0), None)
+    else:
+        rc = lib.gpn_net_forward_pair(_vp(ops), n[0], _vp(slots), _vp(second[0]), n[1], _vp(rbs), n[2], _vp(convs), _vp(second[1]), n[3],
+                                      _vp(bns), _vp(second[2]), n[4], mode, None, ctypes.c_size_t(0), None)
+    return rc, lib.gpn_last_error()
+
+
+def _net_backward(lib, ops, slots, rbs, convs, bns, need_input_grad=1, second=None):
+    lib.gpn_last_error.restype = ctypes.c_char_p
+    n = (len(ops), len(slots), len(rbs), len(convs), len(bns))
+    if second is None:
+        rc = lib.gpn_net_backward(_vp(ops), n[0], _vp(slots), n[1], _vp(rbs), n[2], _vp(convs), n[3], _vp(bns), n[4], 1, need_input_grad,
+                                  None, ctypes.c_size_t(0), None)
+    else:
+        rc = lib.gpn_net_backward_pair(_vp(ops), n[0], _vp(slots), _vp(second[0]), n[1], _vp(rbs), n[2], _vp(convs), _vp(second[1]), n[3],
+                                       _vp(bns), _vp(second[2]), n[4], 1, need_input_grad, None, ctypes.c_size_t(0), None)
+    return rc, lib.gpn_last_error()
+
+
+@pytest.mark.parametrize("mode", [INFERENCE, 0])
+@pytest.mark.parametrize("field", ["weight", "bias"])
+@pytest.mark.parametrize("paired", [False, True])
+def test_executor_forward_rejects_an_eval_batchnorm_without_its_affine_vectors(lib, mode, field, paired):
+    """a BatchNorm over running statistics needs weight and bias too, folded into the conv before it (inference) or not (eval):
+    a null one is GPN_ERR_ARG naming the op, not a device fault in the conv epilogue; in a pair, the second network's counts"""
+    ops, slots, rbs, convs, bns = _net_tables("conv_bn")
+    rc, msg = _net_forward(lib, ops, slots, rbs, convs, bns, mode, (slots, convs, bns) if paired else None)
+    assert rc == ERR_WS, msg  # the tables are good: only the workspace is missing
+    broken = bns.copy()
+    broken[field][0] = 0
+    rc, msg = _net_forward(lib, ops, slots, rbs, convs, bns, mode, (slots, convs, broken)) if paired else \
+        _net_forward(lib, ops, slots, rbs, convs, broken, mode)
+    assert rc == ERR_ARG and b"op 1" in msg and b"BatchNorm needs weight, bias" in msg, msg
+
+
+def test_executor_forward_rejects_a_null_activation_of_the_last_op(lib):
+    ops, slots, rbs, convs, bns = _net_tables("residual")
+    assert _net_forward(lib, ops, slots, rbs, convs, bns, 1)[0] == ERR_WS
+    slots["data"][4] = 0  # the destination of the last op: every launch before it would have been enqueued
+    rc, msg = _net_forward(lib, ops, slots, rbs, convs, bns, 1)
+    assert rc == ERR_ARG and b"op 3" in msg and b"null activation pointer" in msg, msg
+
+
+def test_executor_backward_validates_the_whole_reverse_walk_first(lib):
+    """the pointer checks of the backward pass follow the gradient states through a dry walk of the program, before the weights
+    are packed and before the weight-gradient worker is started"""
+    ops, slots, rbs, convs, bns = _net_tables("conv_bn")
+    ops = ops[:1]  # one CONV, slot 0 -> slot 1, whose output holds the loss gradient
+    slots["grad_state"][1] = 1
+    assert _net_backward(lib, ops, slots, rbs, convs, bns)[0] == ERR_WS
+
+    rb = rbs.copy()
+    rb["pair_src"] = 0  # dW is set: the weight gradient needs the pair lists
+    rc, msg = _net_backward(lib, ops, slots, rb, convs, bns)
+    assert rc == ERR_ARG and b"op 0" in msg and b"pair lists" in msg, msg
+    no_dw = convs.copy()
+    no_dw["dW"] = 0
+    assert _net_backward(lib, ops, slots, rb, no_dw, bns)[0] == ERR_WS
+
+    rb = rbs.copy()
+    rb["nbr_t"] = 0  # needed only where an input gradient is
+    rc, msg = _net_backward(lib, ops, slots, rb, convs, bns, need_input_grad=1)
+    assert rc == ERR_ARG and b"op 0" in msg and b"transposed table" in msg, msg
+    assert _net_backward(lib, ops, slots, rb, convs, bns, need_input_grad=0)[0] == ERR_WS
+
+    s = slots.copy()
+    s["grad"][0] = 0
+    rc, msg = _net_backward(lib, ops, s, rbs, convs, bns)
+    assert rc == ERR_ARG and b"op 0" in msg and b"null gradient buffer" in msg, msg
+
+    # the two networks of a pair must agree on which slots hold a gradient
+    other = slots.copy()
+    other["grad_state"][1] = 0
+    rc, msg = _net_backward(lib, ops, slots, rbs, convs, bns, second=(other, convs, bns))
+    assert rc == ERR_ARG and b"op 0" in msg and b"gradient states differ" in msg, msg
+    assert _net_backward(lib, ops, slots, rbs, convs, bns, second=(slots, convs, bns))[0] == ERR_WS
+
+
+def test_executor_backward_rejects_a_batchnorm_input_consumed_twice(lib):
+    ops, slots, rbs, convs, bns = _net_tables("conv_bn")
+    slots["grad_state"][2] = 1
+    assert _net_backward(lib, ops, slots, rbs, convs, bns)[0] == ERR_WS
+    slots["grad_state"][1] = 1  # the BatchNorm's input already holds a gradient
+    rc, msg = _net_backward(lib, ops, slots, rbs, convs, bns)
+    assert rc == ERR_ARG and b"op 1" in msg and b"consumed twice" in msg, msg
+
+
+def test_executor_backward_skips_ops_nothing_flows_back_through(lib):
+    """an op whose output holds no gradient is skipped by the pass, so the dry walk asks nothing of its pointers"""
+    import numpy as np
+    from gapartnet_amd.network import net_exec as NX
+    ops, slots, rbs, convs, bns = _net_tables("conv_bn")
+    ops = np.concatenate([ops, ops[:1]])  # CONV 0 -> 1, BN 1 -> 2, and a second CONV 0 -> 3 that does not reach the loss
+    slots = np.concatenate([slots, slots[:1]])
+    ops["dst"][2] = 3
+    slots["grad_state"][2] = 1
+    slots["grad"][3] = slots["data"][3] = 0
+    rc, msg = _net_backward(lib, ops, slots, rbs, convs, bns)
+    assert rc == ERR_WS, msg
+    slots["grad_state"][3] = 1  # ... and once it does, they are asked for
+    rc, msg = _net_backward(lib, ops, slots, rbs, convs, bns)
+    assert rc == ERR_ARG and b"op 2" in msg, msg
+
+
+# By (program, rows, channels): gpn_net_ws_bytes, gpn_net_forward_bf16_ws_bytes, and the bytes a training forward / a backward
+# pass ask for ("workspace too small (N needed"), as one network and as a pair.  Recorded at commit b915b6f, the last one before the
+# executor took every workspace address and size from one layout struct: that change must not move a byte.
+WS_BYTES_AT_B915B6F = {
+    ("conv_bn", 100, 16): (110848, 17152, 76800, 110848, 120832, 188928),
+    ("conv_bn", 100, 32): (332288, 61696, 208896, 332288, 352256, 599040),
+    ("conv_bn", 20000, 16): (5338112, 653824, 76800, 5338112, 120832, 10643456),
+    ("conv_bn", 20000, 32): (6307840, 1335296, 208896, 6307840, 352256, 12550144),
+    ("residual", 100, 16): (182528, 34304, 120832, 182528, 208896, 332288),
+    ("residual", 100, 32): (586240, 123392, 352256, 586240, 638976, 1106944),
+    ("residual", 20000, 16): (9363456, 1307648, 120832, 9363456, 208896, 18694144),
+    ("residual", 20000, 32): (9990144, 2670592, 352256, 9990144, 638976, 19914752),
+    ("concat", 100, 16): (244224, 54528, 148480, 244224, 264192, 455680),
+    ("concat", 100, 32): (820224, 191488, 462848, 820224, 860160, 1574912),
+    ("concat", 20000, 16): (10671104, 2601472, 148480, 10671104, 264192, 21309440),
+    ("concat", 20000, 32): (12660736, 5285888, 462848, 12660736, 860160, 25255936),
+}
+
+
+@pytest.mark.parametrize("program,rows,C", sorted(WS_BYTES_AT_B915B6F))
+def test_executor_workspace_sizes_are_unchanged(lib, program, rows, C):
+    lib.gpn_net_ws_bytes.restype = lib.gpn_net_forward_bf16_ws_bytes.restype = ctypes.c_size_t
+    ops, slots, rbs, convs, bns = _net_tables(program, rows, C)
+    args = (_vp(ops), len(ops), _vp(slots), len(slots), _vp(rbs), _vp(convs))
+    got = [lib.gpn_net_ws_bytes(*args), lib.gpn_net_forward_bf16_ws_bytes(*args)]
+    slots["grad_state"][-1] = 1  # the output slot holds the loss gradient
+    for second in (None, (slots, convs, bns)):
+        for rc, msg in (_net_forward(lib, ops, slots, rbs, convs, bns, 1, second),
+                        _net_backward(lib, ops, slots, rbs, convs, bns, 1, second)):
+            assert rc == ERR_WS, msg
+            got.append(int(re.search(rb"\((\d+) needed", msg).group(1)))
+    assert tuple(got) == WS_BYTES_AT_B915B6F[(program, rows, C)]
