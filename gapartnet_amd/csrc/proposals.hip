@@ -308,9 +308,9 @@ __global__ __launch_bounds__(kThreads) void prop_finish_kernel(const int32_t* __
 //          cell among the proposal's voxels (the stride-2 rulebook's trick, rulebook.hip), exclusive sum of the cell counts =
 //          first position of a cell; then the points in order, 256 at a time: position = cell start + points of the cell in
 //          earlier chunks + earlier points of the cell in this chunk (stable, no sort).
-// Bit-equal to the sort path (tests/test_gpu_proposals.py compare both with the oracle).  GPN_PROPOSALS_REVOX=0 / a grid of
-// more than kRevoxMaxCells cells: the sort path.
-constexpr int kRevoxMaxCells = 32768;  // (fullscale <= 30)
+// Bit-equal to the sort path (tests/test_gpu_proposals.py compare both with the oracle; tests/test_gpu_proposal_seams.py both
+// with a plain reference).  There is no switch: a grid of more than kRevoxMaxCells cells takes the sort path, every other this one.
+constexpr int kRevoxMaxCells = 32768;  // (fullscale <= 31: its (31 + 1)^3 cells fill the bitmap exactly)
 constexpr int kRevoxWords = kRevoxMaxCells / 32;
 
 struct RevoxCell {
@@ -654,7 +654,9 @@ int proposal_tail(const float* pt_xyz_p, const int64_t* proposal_indices, const 
                      voxel_coords4, counts);
   GPN_CHECK_LAUNCH();
   // rows of the proposal grid's coarse level (the ScoreNet / NPCS-Net U-Nets have one stride-2 level): with it in the same
-  // read as the other counts, building their rulebooks needs no host read of its own
+  // read as the other counts, building their rulebooks needs no host read of its own.  Counted by the rulebook builders' rule:
+  // distinct (proposal, x / 2, y / 2, z / 2) rows INSIDE the coarse grid of floor(fullscale / 2)^3 cells - with an odd fullscale
+  // the voxels in the last plane of an axis (x == fullscale - 1) have no coarse cell and do not count
   const int32_t grid_shape[3] = {(int32_t)fullscale, (int32_t)fullscale, (int32_t)fullscale};
   return gpn_rulebook_level_counts(voxel_coords4, T2, counts + kV, P_ub > 0 ? P_ub : 1, grid_shape, 1, counts + kCoarse, sub, sub_bytes,
                                    (gpn_stream_t)stream);

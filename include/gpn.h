@@ -623,7 +623,10 @@ int gpn_npcs_loss_bwd(const float* logits, int n_cls3, const float* gt_npcs, con
  * K1 / K2 neighbours, label-aware) -> proposals of >= min_points points, ordered by their first point, members ascending,
  * set A's proposals before set B's -> per-proposal frame (centre, scale <= max_scale, jittered shift) -> fullscale^3 voxel
  * grid per proposal.  Nothing is read back: every output has its upper-bound capacity and counts [8] i64 (device) holds
- * {Q valid points, M proposal points, P proposals, V voxels, points dropped by the voxeliser, ...}.
+ * {Q valid points, M proposal points, P proposals, V voxels, points dropped by the voxeliser, (internal), rows of the grid's
+ * stride-2 level, (unused)}.  The stride-2 rows are counted as gpn_rulebook_level_counts counts them: distinct
+ * (proposal, x/2, y/2, z/2) rows inside the coarse grid of floor(fullscale/2)^3 cells, so with an odd fullscale the voxels
+ * at x == fullscale - 1 (any axis) do not count.
  * Outputs (capacity): valid_mask [N] u8, valid_indices [N] i64; per proposal point [2N]: sorted_indices i64 (numbering
  * among the valid points, as the reference), point_indices i64 (row of `points`), proposal_indices i64, batch_indices_p
  * i32, pt_xyz_p [.,3] f32, sem_preds_p i32, instance_labels_p i32, pc_voxel_id i32, point_order i32 (+ voxel_point_start
