@@ -20,7 +20,7 @@ _SIZE_T_FUNCS = (
     "gpn_pointmlp_wgrad_ws_bytes", "gpn_cloud_nearest_ws_bytes", "gpn_proposals_from_masks_ws_bytes",
     "gpn_render_ws_bytes", "gpn_frame_select_ws_bytes", "gpn_ground_mask_resize_ws_bytes", "gpn_ground_knn_ws_bytes",
     "gpn_cloud_grid_sample_ws_bytes", "gpn_frame_plane_refit_ws_bytes", "gpn_frame_component_select_ws_bytes",
-    "gpn_parts_gather_ws_bytes",
+    "gpn_parts_gather_ws_bytes", "gpn_views_overlap_ws_bytes", "gpn_views_gather_ws_bytes",
 )
 
 

@@ -55,6 +55,8 @@ const char* kEntryPoints[] = {
     "gpn_frame_component_select_ws_bytes", "gpn_frame_component_select",
     "gpn_joint_sample", "gpn_cpd_rigid", "gpn_joint_from_rigid",
     "gpn_parts_overlap", "gpn_parts_match", "gpn_parts_gather_ws_bytes", "gpn_parts_gather",
+    "gpn_views_world", "gpn_views_overlap_lds_parts", "gpn_views_overlap_ws_bytes", "gpn_views_overlap", "gpn_views_merge",
+    "gpn_views_relabel", "gpn_views_gather_ws_bytes", "gpn_views_gather",
     "gpn_pose_gt_fit", "gpn_box_iou_3d", "gpn_pose_pair_errors",
     "gpn_render_max_links", "gpn_render_ws_bytes", "gpn_render_setup", "gpn_render_raster", "gpn_render_annotate",
     "gpn_render_max_lights", "gpn_render_shade",

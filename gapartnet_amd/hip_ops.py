@@ -2179,6 +2179,140 @@ def parts_gather(rows, inst, valid, n_parts, seg_start, n_total, out=None):
     return pc
 
 
+# ---------------------------------------------------------------------------------------------------- MV (posed views)
+VIEWS_MAX = 64
+FUSE_PARTS_MAX = 512
+
+
+def _view_dims(t, what):
+    V, H, W = _frame_dims(t)
+    if V > VIEWS_MAX:
+        raise _C.GpnError(f"{what}: at most {VIEWS_MAX} views, got {V}")
+    return V, H, W
+
+
+def _fuse_width(GT, what):
+    GT = int(GT)
+    if not 0 <= GT <= FUSE_PARTS_MAX:
+        raise _C.GpnError(f"{what}: at most {FUSE_PARTS_MAX} parts over all views, got {GT}")
+    return GT
+
+
+def views_world(rows, valid, inst, n_parts, R, t, GT):
+    """member pixels -> the world frame (include/gpn.h section MV): rows [V*H*W,6] f32 and valid [V,H,W] u8 of frame_backproject
+    (flip = 0), inst [V,H,W] i32 / i64, n_parts [V], R [V,3,3], t [V,3] f64 (a camera point is (world - t) @ R), GT = the table
+    width -> (wrows [V*H*W,3] f32, part_of [V,H,W] i32, area [GT] i32, lo [3] f64) on the device"""
+    dev = _dev(rows, valid, inst, R, t)
+    V, H, W = _view_dims(inst, "views_world")
+    GT = _fuse_width(GT, "views_world")
+    if inst.dtype != torch.int32:  # (every value outside 0 .. 511 belongs to no part; a plain cast of an int64 would wrap)
+        inst = inst.to(torch.int64).clamp(-1, FUSE_PARTS_MAX).to(torch.int32)
+    inst, valid, rows = inst.contiguous(), _c(valid, torch.uint8), _c(rows, torch.float32)
+    R, t = _c(R, torch.float64), _c(t, torch.float64)
+    if tuple(valid.shape) != (V, H, W) or rows.numel() != V * H * W * 6 or R.numel() != V * 9 or t.numel() != V * 3:
+        raise _C.GpnError("views_world: valid [V,H,W], one row per pixel, R [V,3,3] and t [V,3]")
+    n_parts = _part_counts(n_parts, V, dev, "views_world")
+    wrows = torch.empty((V * H * W, 3), dtype=torch.float32, device=dev)
+    part_of = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+    area = torch.empty((GT,), dtype=torch.int32, device=dev)
+    lo = torch.empty((3,), dtype=torch.float64, device=dev)
+    check(_C.lib().gpn_views_world(ptr(rows), ptr(valid), ptr(inst), ptr(n_parts), ptr(R), ptr(t), i32(V), i32(H), i32(W), i32(GT),
+                                   ptr(wrows), ptr(part_of), ptr(area), ptr(lo), _stream()), "gpn_views_world")
+    return wrows, part_of, area, lo
+
+
+def views_overlap(wrows, part_of, lo, cell, GT, want_keys=False):
+    """the occupancy tables on the 1024-cell grid (section MV): -> (vol [GT], inter [GT,GT], dropped [V]) i32 on the device, and the
+    pixels' keys [V,H,W] as int64 bit patterns with ``want_keys``"""
+    dev = _dev(wrows, part_of, lo)
+    V, H, W = _view_dims(part_of, "views_overlap")
+    GT = _fuse_width(GT, "views_overlap")
+    wrows, part_of, lo = _c(wrows, torch.float32), _c(part_of, torch.int32), _c(lo, torch.float64)
+    if wrows.numel() != V * H * W * 3 or lo.numel() != 3:
+        raise _C.GpnError("views_overlap: one world row per pixel and lo [3]")
+    vol = torch.empty((GT,), dtype=torch.int32, device=dev)
+    inter = torch.empty((GT, GT), dtype=torch.int32, device=dev)
+    dropped = torch.empty((V,), dtype=torch.int32, device=dev)
+    keys = torch.empty((V, H, W), dtype=torch.int64, device=dev) if want_keys else None
+    L = _C.lib()
+    ws = _ws(L.gpn_views_overlap_ws_bytes(i32(V), i32(H), i32(W)), dev)
+    check(L.gpn_views_overlap(ptr(wrows), ptr(part_of), ptr(lo), _dbl(float(cell)), i32(V), i32(H), i32(W), i32(GT), ptr(vol), ptr(inter),
+                              ptr(dropped), ptr(keys), ptr(ws), szt(ws.numel()), _stream()), "gpn_views_overlap")
+    return (vol, inter, dropped, keys) if want_keys else (vol, inter, dropped)
+
+
+def views_overlap_lds_parts(parts=-1):
+    """the largest GT whose pair table gpn_views_overlap sums in LDS (negative: query)"""
+    return int(_C.lib().gpn_views_overlap_lds_parts(i32(parts)))
+
+
+def views_merge(inter, vol, cls, n_parts, min_inter=4, min_overlap=0.25):
+    """the greedy single-linkage merge of section MV: inter [GT,GT], vol [GT], cls [GT] or None, n_parts [V] -> dict(fused_of [GT],
+    n_fused [1], fused_views [GT] (uint64 bit patterns in int64), fused_class [GT], fused_vol [GT], fused_parts [GT,V], links [GT,3],
+    n_links [1]) on the device"""
+    dev = _dev(inter, vol)
+    GT = _fuse_width(vol.numel(), "views_merge")
+    inter, vol = _c(inter, torch.int32), _c(vol, torch.int32)
+    if inter.numel() != GT * GT:
+        raise _C.GpnError("views_merge: inter is [GT,GT]")
+    V = len(n_parts)
+    if V > VIEWS_MAX:
+        raise _C.GpnError(f"views_merge: at most {VIEWS_MAX} views, got {V}")
+    n_parts = _part_counts(n_parts, V, dev, "views_merge")
+    if cls is not None:
+        cls = _c(cls.to(dev, non_blocking=True), torch.int32)
+        if cls.numel() != GT:
+            raise _C.GpnError("views_merge: cls is [GT]")
+    i32t = torch.int32
+    out = dict(fused_of=torch.empty((GT,), dtype=i32t, device=dev), n_fused=torch.empty((1,), dtype=i32t, device=dev),
+               fused_views=torch.empty((GT,), dtype=torch.int64, device=dev), fused_class=torch.empty((GT,), dtype=i32t, device=dev),
+               fused_vol=torch.empty((GT,), dtype=i32t, device=dev), fused_parts=torch.empty((GT, V), dtype=i32t, device=dev),
+               links=torch.empty((GT, 3), dtype=i32t, device=dev), n_links=torch.empty((1,), dtype=i32t, device=dev))
+    check(_C.lib().gpn_views_merge(ptr(inter), ptr(vol), ptr(cls), ptr(n_parts), i32(V), i32(GT), i32(min_inter), _dbl(float(min_overlap)),
+                                   ptr(out["fused_of"]), ptr(out["n_fused"]), ptr(out["fused_views"]), ptr(out["fused_class"]),
+                                   ptr(out["fused_vol"]), ptr(out["fused_parts"]), ptr(out["links"]), ptr(out["n_links"]), _stream()),
+          "gpn_views_merge")
+    return out
+
+
+def views_relabel(part_of, fused_of):
+    """fused_inst [V,H,W] i32 = fused_of[part_of], or -1 (section MV)"""
+    dev = _dev(part_of, fused_of)
+    V, H, W = _view_dims(part_of, "views_relabel")
+    part_of, fused_of = _c(part_of, torch.int32), _c(fused_of, torch.int32)
+    GT = _fuse_width(fused_of.numel(), "views_relabel")
+    fused_inst = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+    check(_C.lib().gpn_views_relabel(ptr(part_of), ptr(fused_of), i32(V), i32(H), i32(W), i32(GT), ptr(fused_inst), _stream()),
+          "gpn_views_relabel")
+    return fused_inst
+
+
+def views_gather(wrows, npcs, fused_inst, seg_start, n_total):
+    """the fused parts' clouds (section MV): wrows [V*H*W,3] f32, npcs [V,H,W,3] f32 or None, fused_inst [V,H,W] i32, seg_start [F] i64
+    (negative: drop the part) -> (xyz [M,3] f64, npcs_out [M,3] f64 or None, src [M] i64); rows no segment covers are not written"""
+    dev = _dev(wrows, fused_inst)
+    V, H, W = _view_dims(fused_inst, "views_gather")
+    wrows, fused_inst = _c(wrows, torch.float32), _c(fused_inst, torch.int32)
+    seg_start = _c(seg_start.to(dev, non_blocking=True), torch.int64).reshape(-1)
+    F = _fuse_width(seg_start.numel(), "views_gather")
+    M = int(n_total)
+    if wrows.numel() != V * H * W * 3:
+        raise _C.GpnError("views_gather: one world row per pixel")
+    if npcs is not None:
+        _dev(npcs)
+        npcs = _c(npcs, torch.float32)
+        if npcs.numel() != V * H * W * 3:
+            raise _C.GpnError("views_gather: npcs is [V,H,W,3]")
+    xyz = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    npcs_out = torch.empty((M, 3), dtype=torch.float64, device=dev) if npcs is not None else None
+    src = torch.empty((M,), dtype=torch.int64, device=dev)
+    L = _C.lib()
+    ws = _ws(L.gpn_views_gather_ws_bytes(i32(V), i32(H), i32(W), i32(F)), dev)
+    check(L.gpn_views_gather(ptr(wrows), ptr(npcs), ptr(fused_inst), ptr(seg_start), i32(V), i32(H), i32(W), i32(F), i64(M), ptr(xyz),
+                             ptr(npcs_out), ptr(src), ptr(ws), szt(ws.numel()), _stream()), "gpn_views_gather")
+    return xyz, npcs_out, src
+
+
 # ---------------------------------------------------------------------------------------------------- PE (pose evaluation)
 def pose_gt_fit(xyz, npcs, slot, scene_offsets, W):
     """xyz, npcs [N,3] f32, slot [N] i32 (scene * W + instance id, negative = none), scene_offsets [S+1] i64 -> dict per slot

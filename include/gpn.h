@@ -1268,6 +1268,78 @@ int gpn_parts_gather(const float* rows, const int32_t* inst, const uint8_t* vali
                      int V, int H, int W, int P, int64_t n_total, double* pc, void* ws, size_t ws_bytes, gpn_stream_t stream);
 
 /* ================================================================================================
+ * MV - the part predictions of several POSED views of one object fused into object parts: one list of parts in the world frame,
+ * every part knowing its mask in every view, its cloud the union of all views' member points (NPCS is canonical per part, so the
+ * union is a valid input to gpn_pose_fit).  The reference has no counterpart (ObjIns holds one image); the contract is this
+ * project's own.  ONE object per call: V views of one size H x W, 1 <= V <= GPN_VIEWS_MAX (V * H * W < 2^31 - 1024), GT parts over
+ * all views, GT <= GPN_FUSE_PARTS_MAX (more is an argument error).  The rules of sections FR and AR hold: no host read inside an
+ * entry point; no float atomics; integer atomics only where the result does not depend on their order (minima, histograms,
+ * counters); every output is bit-reproducible.  V == 0 and GT == 0 are valid calls that launch nothing or write empty tables (with
+ * GT == 0 and V > 0 the per-pixel outputs are still written: no pixel is a member).  Argument errors return 1 without touching the
+ * device.
+ * INPUT: rows [V*H*W,6] f32 and valid [V,H,W] u8 as gpn_frame_backproject writes them with flip = 0; inst [V,H,W] i32 and n_parts [V]
+ *   i32 on the device, MEMBERSHIP exactly as in section AR (a count is read as min(max(n_parts[v], 0), GT)); R [V,3,3], t [V,3]
+ *   f64 in the renderer's convention (camera_frame, dataset/render_assets.py): a camera point is (world - t) @ R, so
+ *   world = cam @ R^T + t.  GLOBAL PART ID g = base[v] + p with base the exclusive scan of the counts; a part with g >= GT does not
+ *   exist (its pixels are members of nothing).
+ * gpn_views_world: for every member pixel, in float64, in this order, without fused multiply-add,
+ *     w_k = ((x * R[k][0] + y * R[k][1]) + z * R[k][2]) + t[k]      (x, y, z = the float32 row cast up)
+ *   wrows [V*H*W,3] f32 = (float)w, NaN (all three) for a non-member pixel; part_of [V,H,W] i32 = g or -1; area [GT] i32 = the member
+ *   pixels of each part; lo [3] f64 = (double) of the smallest stored float32 per axis over all member pixels, by atomicMin on the
+ *   order-preserving integer image (so -0.0 < +0.0; a member's row is finite whenever R and t are), 0.0 when no pixel is a member.
+ * gpn_views_overlap: the occupancy tables on a fixed grid of 1024 cells an axis.  cell > 0 (f64);
+ *     i_k = floor(((double)wrows_k - lo_k) / cell)                    (one subtraction, one division)
+ *   a member pixel with any i_k outside 0 .. 1023 (or NaN) is DROPPED from the occupancy and counted in dropped [V] i32; it stays a
+ *   member for everything else.  vox = i_x << 20 | i_y << 10 | i_z; key = vox << 9 | g, all ones for a non-member or dropped pixel
+ *   (keys_out [V*H*W] u64 receives the keys when it is not NULL).  Over the set of distinct (vox, g): vol [GT] i32 = the distinct
+ *   voxels of part g; inter [GT,GT] i32, symmetric, zero diagonal: (g, h) = the voxels that hold both g and h, pairs of one view
+ *   included.  How: ONE rocprim::radix_sort_keys over 40 bits (the 39 live ones and the bit that puts the all-ones key last),
+ *   rocprim::unique, then one lane per distinct entry: vol[g] += 1 and one pair of increments for every LATER entry of its voxel
+ *   (a voxel holds at most GT entries).  The pair increments are summed in an LDS table while GT * GT * 4 bytes fit in 64 KiB
+ *   (GT <= 128) and flushed by global integer adds, and go to global memory directly above that; gpn_views_overlap_lds_parts(n)
+ *   moves that switch (n < 0: query; the bound 128 stays) - both forms give the same tables.  Workspace: gpn_views_overlap_ws_bytes.
+ * gpn_views_merge: one workgroup.  cls [GT] i32 (NULL: all equal); view_of[g] from the scan of n_parts (a g beyond the scan's end
+ *   has no view and counts as vol == 0).  A pair g < h is ELIGIBLE iff cls[g] == cls[h], inter[g,h] >= max(min_inter, 1),
+ *   (double)inter[g,h] >= min_overlap * (double)min(vol[g], vol[h]) (one float64 product, one comparison) and, at the time it is
+ *   considered, g and h lie in different clusters whose view sets (one uint64 mask a cluster) are disjoint.  Repeatedly the
+ *   eligible pair with the largest inter / min(vol) is taken - compared exactly by the 64-bit cross products (inter < 2^30, so
+ *   below 2^60), ties to the smaller g, then the smaller h - its clusters are united and their view masks ORed, until no eligible
+ *   pair is left.  Clusters only grow, so a pair refused for its view sets stays refused: the loop equals one pass over the
+ *   candidates in that total order, and the result is unique.  DECISION: single linkage, greedy, at most one part per view in a
+ *   fused part; normalised by the SMALLER volume, because two views see different faces of one part; not an optimal assignment.
+ *   Outputs: fused_of [GT] i32 = fused id 0 .. F-1 in ascending order of each cluster's smallest g, -1 for a part with vol == 0;
+ *   n_fused [1] i32 = F; per fused id [GT]: fused_views u64, fused_class i32 (the members' class, 0 with cls == NULL), fused_vol i32
+ *   (the sum of the members' vol), fused_parts [GT,V] i32 (the LOCAL part of each view, or -1); links [GT,3] i32 = (g, h, inter) of
+ *   every union in the order taken, n_links [1] i32.  Entries at or beyond F: fused_views 0, fused_class -1, fused_vol 0,
+ *   fused_parts -1; links at or beyond n_links: (-1, -1, 0).
+ * gpn_views_relabel: fused_inst [V,H,W] i32 = fused_of[part_of], or -1: ids consistent across views.
+ * gpn_views_gather: npcs [V,H,W,3] f32 (NULL together with npcs_out: none), seg_start [F] i64 = the first output row of fused part f
+ *   or negative to drop it, F <= GPN_FUSE_PARTS_MAX.  The pixels with fused_inst == f go to rows seg_start[f] + 0, 1, 2, ... in
+ *   ascending (view, pixel) order: xyz [M,3] f64 = the wrows cast up, npcs_out [M,3] f64, src [M] i64 = v * H * W + pixel.  Rows no
+ *   segment covers, and rows at or beyond M = n_total, are not written.  How: the stable multi-way partition of gpn_parts_gather
+ *   over 9-bit keys, the counts scanned over (view, chunk) per fused part.  Workspace: gpn_views_gather_ws_bytes.
+ * ================================================================================================ */
+#define GPN_VIEWS_MAX 64
+#define GPN_FUSE_PARTS_MAX 512
+int gpn_views_world(const float* rows, const uint8_t* valid, const int32_t* inst, const int32_t* n_parts, const double* R,
+                    const double* t, int V, int H, int W, int GT, float* wrows, int32_t* part_of, int32_t* area, double* lo,
+                    gpn_stream_t stream);
+int gpn_views_overlap_lds_parts(int parts);
+size_t gpn_views_overlap_ws_bytes(int V, int H, int W);
+int gpn_views_overlap(const float* wrows, const int32_t* part_of, const double* lo, double cell, int V, int H, int W, int GT,
+                      int32_t* vol, int32_t* inter, int32_t* dropped, uint64_t* keys_out, void* ws, size_t ws_bytes,
+                      gpn_stream_t stream);
+int gpn_views_merge(const int32_t* inter, const int32_t* vol, const int32_t* cls, const int32_t* n_parts, int V, int GT, int min_inter,
+                    double min_overlap, int32_t* fused_of, int32_t* n_fused, uint64_t* fused_views, int32_t* fused_class,
+                    int32_t* fused_vol, int32_t* fused_parts, int32_t* links, int32_t* n_links, gpn_stream_t stream);
+int gpn_views_relabel(const int32_t* part_of, const int32_t* fused_of, int V, int H, int W, int GT, int32_t* fused_inst,
+                      gpn_stream_t stream);
+size_t gpn_views_gather_ws_bytes(int V, int H, int W, int F);
+int gpn_views_gather(const float* wrows, const float* npcs, const int32_t* fused_inst, const int64_t* seg_start, int V, int H, int W,
+                     int F, int64_t n_total, double* xyz, double* npcs_out, int64_t* src, void* ws, size_t ws_bytes,
+                     gpn_stream_t stream);
+
+/* ================================================================================================
  * PE - pose evaluation: is an estimated part pose right?  The ground-truth pose of every instance, the exact IoU of two oriented
  * boxes, and the errors of matched (prediction, ground truth) pairs under the part's symmetry group: what the GAPartNet paper
  * reports for its second task (R_e, T_e, S_e, 3D IoU).  The reference has no counterpart (on_test_epoch_end ends at a
