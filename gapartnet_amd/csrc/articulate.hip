@@ -5,23 +5,19 @@
 //            first groups its lanes by key (ballots) and adds each group's popcount with ONE LDS atomic; non-zero bins are merged
 //            into the frame pair's table by integer global adds.
 //   match    greedy one-to-one matching by exact IoU: one workgroup a frame pair, the table in LDS, one arg-max a round.
-//   gather   a stable multi-way partition of every frame's pixels by part: per-chunk per-part counts, one scan over the chunks per
-//            (frame, part), then ordered stores - the rank of a pixel among the earlier pixels of its own part comes from ballots
-//            over equal keys inside a wave and from LDS counters added in (slot, wave) order across the chunk.
+//   gather   the stable multi-way partition of pixel_parts.h over 6-bit keys (the part of a pixel): counts [V][P][chunk], one scan
+//            over the chunks per (frame, part), the xyz of a member row stored as float64.
+// The wave helpers (wave_hist_add, wave_match), the partition and the workgroup arg-max (block_best) are pixel_parts.h's, shared with
+// multiview.hip.
 // No float atomics; integer atomics only on histograms (order-free); no host read; every result is independent of timing.
-#include "gpn_common.h"
-#include "wg_scan.h"
+#include "pixel_parts.h"
 
 namespace {
 
 using namespace gpn;
+using namespace gpn::pp;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;  // pixels per thread: pixel = chunk * kChunk + e * kThreads + tid
-constexpr int kChunk = kThreads * kPer;
 constexpr int kMaxP = GPN_PARTS_MAX;
-constexpr int kGroupRounds = 8;  // key groups a wave resolves by ballots before its remaining lanes add one by one
 
 // the membership rule: the part of pixel g, or -1.  n is the frame's live part count, already clamped to the table width.
 __device__ __forceinline__ int part_key(const int32_t* __restrict__ inst, const uint8_t* __restrict__ valid, int64_t g, bool inside,
@@ -29,32 +25,6 @@ __device__ __forceinline__ int part_key(const int32_t* __restrict__ inst, const 
   if (!inside) return -1;
   const int p = inst[g];
   return (valid[g] != 0 && p >= 0 && p < n) ? p : -1;
-}
-
-// bins[key] += 1 for every lane with key >= 0, one LDS atomic per group of equal keys.  Called by whole waves.
-__device__ __forceinline__ void wave_hist_add(int* bins, int key) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(key >= 0);
-  for (int round = 0; todo != 0ull && round < kGroupRounds; ++round) {  // (todo is wave-uniform)
-    const int lead = __ffsll((long long)todo) - 1;
-    const int k = __shfl(key, lead, 64);
-    const unsigned long long same = __ballot(key == k);
-    if (lane == lead) atomicAdd(&bins[k], __popcll(same));
-    todo &= ~same;
-  }
-  if ((todo >> lane) & 1ull) atomicAdd(&bins[key], 1);
-}
-
-// the lanes of the wave whose key (0 .. 63, `ok` lanes only) equals this lane's: seven ballots.  0 for a lane that is not ok.
-__device__ __forceinline__ unsigned long long wave_match6(int key, bool ok) {
-  unsigned long long same = __ballot(ok);
-#pragma unroll
-  for (int b = 0; b < 6; ++b) {
-    const bool bit = ((key >> b) & 1) != 0;
-    const unsigned long long m = __ballot(ok && bit);
-    same &= bit ? m : ~m;
-  }
-  return ok ? same : 0ull;
 }
 
 // ---- overlap ----------------------------------------------------------------------------------------------------------------------
@@ -92,18 +62,7 @@ __global__ __launch_bounds__(kThreads) void ar_overlap_kernel(const int32_t* __r
 }
 
 // ---- match ------------------------------------------------------------------------------------------------------------------------
-struct Cand {
-  int inter, uni, e;  // e = i * PB + j, -1 = none
-};
-// a better than b: the larger IoU by 64-bit cross-multiplication, ties to the smaller (i, j)
-__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
-  if (a.e < 0) return false;
-  if (b.e < 0) return true;
-  const long long l = (long long)a.inter * b.uni, r = (long long)b.inter * a.uni;
-  if (l != r) return l > r;
-  return a.e < b.e;
-}
-
+// a candidate: num = inter, den = union, e = i * PB + j.  The larger IoU first, ties to the smaller (i, j).
 __global__ __launch_bounds__(kThreads) void ar_match_kernel(const int32_t* __restrict__ inter, const int32_t* __restrict__ area_a,
                                                             const int32_t* __restrict__ area_b, const int32_t* __restrict__ n_a,
                                                             const int32_t* __restrict__ n_b, const int32_t* __restrict__ cls_a,
@@ -113,9 +72,8 @@ __global__ __launch_bounds__(kThreads) void ar_match_kernel(const int32_t* __res
                                                             int32_t* __restrict__ m_union) {
   __shared__ int tab[kMaxP * kMaxP];  // inter of the eligible pairs, 0 elsewhere
   __shared__ int aa[kMaxP], ab[kMaxP], mab[kMaxP], mba[kMaxP], mi[kMaxP], mu[kMaxP];
-  __shared__ Cand wbest[kWaves];
-  __shared__ int won;
-  const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ RatioCand wbest[kWaves];
+  const int v = blockIdx.x, tid = threadIdx.x;
   const int na = min(max(n_a[v], 0), PA), nb = min(max(n_b[v], 0), PB);
   const int nbins = PA * PB;
   if (tid < kMaxP) {
@@ -141,41 +99,26 @@ __global__ __launch_bounds__(kThreads) void ar_match_kernel(const int32_t* __res
   __syncthreads();
   int matched = 0;
   const int rounds = min(na, nb);
-  for (int round = 0; round < rounds; ++round) {  // (workgroup-uniform: the exit below is read from LDS by every thread)
-    Cand best{0, 1, -1};
+  for (int round = 0; round < rounds; ++round) {  // (workgroup-uniform: block_best hands every thread the same winner)
+    RatioCand best{0, 1, -1};
     for (int e = tid; e < nbins; e += kThreads) {
       const int c = tab[e];
       if (c == 0) continue;
       const int i = e / PB, j = e - i * PB;
       if (mab[i] >= 0 || mba[j] >= 0) continue;
-      const Cand cand{c, aa[i] + ab[j] - c, e};
-      if (cand_better(cand, best)) best = cand;
+      const RatioCand cand{c, aa[i] + ab[j] - c, e};
+      if (ratio_better(cand, best)) best = cand;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      Cand o;
-      o.inter = __shfl_xor(best.inter, off, 64);
-      o.uni = __shfl_xor(best.uni, off, 64);
-      o.e = __shfl_xor(best.e, off, 64);
-      if (cand_better(o, best)) best = o;
-    }
-    if (lane == 0) wbest[wave] = best;
-    __syncthreads();
+    const RatioCand b = block_best<kWaves>(best, wbest);
+    if (b.e < 0) break;
     if (tid == 0) {
-      Cand b = wbest[0];
-      for (int w = 1; w < kWaves; ++w)
-        if (cand_better(wbest[w], b)) b = wbest[w];
-      won = b.e;
-      if (b.e >= 0) {
-        const int i = b.e / PB, j = b.e - i * PB;
-        mab[i] = j;
-        mba[j] = i;
-        mi[i] = b.inter;
-        mu[i] = b.uni;
-      }
+      const int i = b.e / PB, j = b.e - i * PB;
+      mab[i] = j;
+      mba[j] = i;
+      mi[i] = b.num;
+      mu[i] = b.den;
     }
-    __syncthreads();
-    if (won < 0) break;
+    __syncthreads();  // the next round reads mab and mba, and writes wbest
     ++matched;
   }
   if (tid < PA) {
@@ -188,76 +131,34 @@ __global__ __launch_bounds__(kThreads) void ar_match_kernel(const int32_t* __res
 }
 
 // ---- gather -----------------------------------------------------------------------------------------------------------------------
-// per chunk: the members of every part.  counts [V][P][nchunk]
-__global__ __launch_bounds__(kThreads) void ar_count_kernel(const int32_t* __restrict__ inst, const uint8_t* __restrict__ valid,
-                                                            const int32_t* __restrict__ n_parts, int64_t HW, int P,
-                                                            int32_t* __restrict__ counts) {
-  __shared__ int h[kMaxP];
-  const int v = blockIdx.y, tid = threadIdx.x;
-  const int n = min(max(n_parts[v], 0), P);
-  if (tid < kMaxP) h[tid] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-    const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
-    wave_hist_add(h, part_key(inst, valid, (int64_t)v * HW + p, p < HW, n));
-  }
-  __syncthreads();
-  if (tid < P) counts[((int64_t)v * P + tid) * gridDim.x + blockIdx.x] = h[tid];
-}
-
-// one workgroup per (part, frame): the counts of its chunks -> their exclusive prefix, in place
-__global__ __launch_bounds__(kThreads) void ar_scan_kernel(int32_t* __restrict__ counts, int nchunk) {
-  __shared__ int wsum[kWaves];
-  int32_t* c = counts + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nchunk;
-  block_scan_tiled<kWaves, int>(nchunk, [&](int64_t i) { return c[i]; }, c, wsum);
-}
-
-__global__ __launch_bounds__(kThreads) void ar_store_kernel(const float* __restrict__ rows, const int32_t* __restrict__ inst,
-                                                            const uint8_t* __restrict__ valid, const int32_t* __restrict__ n_parts,
-                                                            const int64_t* __restrict__ seg_start, const int32_t* __restrict__ base,
-                                                            int64_t HW, int P, int64_t n_total, double* __restrict__ pc) {
-  __shared__ int cnt[kPer * kWaves][kMaxP];  // members of a part in (slot e, wave), then the members before that (slot, wave)
-  const int v = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = min(max(n_parts[v], 0), P);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int i = tid; i < kPer * kWaves * kMaxP; i += kThreads) (&cnt[0][0])[i] = 0;
-  __syncthreads();
-  int key[kPer], rank[kPer];
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-    const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
-    key[e] = part_key(inst, valid, (int64_t)v * HW + p, p < HW, n);
-    const unsigned long long same = wave_match6(key[e], key[e] >= 0);
-    rank[e] = __popcll(same & below);
-    if (key[e] >= 0 && rank[e] == 0) cnt[e * kWaves + wave][key[e]] = __popcll(same);  // (the group's lowest lane)
-  }
-  __syncthreads();
-  if (tid < P) {  // (slot order: e first, then the wave)
-    int run = base[((int64_t)v * P + tid) * gridDim.x + blockIdx.x];
-#pragma unroll
-    for (int s = 0; s < kPer * kWaves; ++s) {
-      const int c = cnt[s][tid];
-      cnt[s][tid] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-    if (key[e] < 0) continue;
-    const int64_t s0 = seg_start[(int64_t)v * P + key[e]];
-    if (s0 < 0) continue;
-    const int64_t pos = s0 + cnt[e * kWaves + wave][key[e]] + rank[e];
-    if (pos >= n_total) continue;
-    const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
-    const float* q = rows + ((int64_t)v * HW + p) * 6;
+// the partition's policy: key = the part of a pixel; counts [V][P][nchunk], one scan per (part, frame); a member's xyz as float64
+struct ArParts {
+  static constexpr int kMaxKeys = kMaxP, kKeyBits = 6;
+  const float* rows;
+  const int32_t* inst;
+  const uint8_t* valid;
+  const int32_t* n_parts;
+  const int64_t* seg_start;
+  int P;
+  int64_t n_total;
+  double* pc;
+  __device__ int live_keys(int) const { return P; }
+  __device__ int key(int v, int64_t g, bool inside) const { return part_key(inst, valid, g, inside, min(max(n_parts[v], 0), P)); }
+  __device__ int64_t counts_index(int v, int key, int chunk, int nchunk, int) const { return ((int64_t)v * P + key) * nchunk + chunk; }
+  dim3 scan_grid(int V) const { return dim3((unsigned)P, (unsigned)V); }
+  int64_t scan_len(int, int64_t nchunk) const { return nchunk; }
+  __device__ void store(int v, int key, int rank, int64_t g) const {
+    const int64_t s0 = seg_start[(int64_t)v * P + key];
+    if (s0 < 0) return;
+    const int64_t pos = s0 + rank;
+    if (pos >= n_total) return;
+    const float* q = rows + g * 6;
     double* o = pc + pos * 3;
     o[0] = (double)q[0];
     o[1] = (double)q[1];
     o[2] = (double)q[2];
   }
-}
+};
 
 inline bool frames_ok(int V, int H, int W) { return V >= 0 && V <= 65535 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384; }
 
@@ -317,12 +218,5 @@ extern "C" int gpn_parts_gather(const float* rows, const int32_t* inst, const ui
   gpn::WsCarver carve(ws, ws_bytes);
   int32_t* counts = carve.take<int32_t>((size_t)V * P * nchunk);
   GPN_CHECK_WS(carve);
-  const dim3 grid((unsigned)nchunk, (unsigned)V);
-  hipLaunchKernelGGL(ar_count_kernel, grid, dim3(kThreads), 0, stream, inst, valid, n_parts, HW, P, counts);
-  GPN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ar_scan_kernel, dim3((unsigned)P, (unsigned)V), dim3(kThreads), 0, stream, counts, (int)nchunk);
-  GPN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ar_store_kernel, grid, dim3(kThreads), 0, stream, rows, inst, valid, n_parts, seg_start, counts, HW, P, n_total, pc);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  return pp_partition(ArParts{rows, inst, valid, n_parts, seg_start, P, n_total, pc}, V, HW, counts, stream);
 }

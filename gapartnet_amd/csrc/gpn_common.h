@@ -154,6 +154,28 @@ __device__ __forceinline__ float affine_apply(const ConvAffine& ep, const Affine
   if (ep.relu) v = v > 0.f ? v : 0.f;
   return v;
 }
+// ---- the order-preserving integer image of a float, for integer atomicMin / atomicMax (exact: any order gives the same bits) -------
+// Two families; a buffer stays on the one whose initial values it was filled with.
+// signed: int compare = float compare; the map on the bits is its own inverse.  +inf -> 0x7f800000.
+__device__ __forceinline__ int float_order(float f) {
+  const int i = __float_as_int(f);
+  return i >= 0 ? i : i ^ 0x7fffffff;
+}
+__device__ __forceinline__ float order_float(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+// unsigned: uint32 / uint64 compare = float / double compare.  No number maps to all ones (a memset of 0xff is "no minimum yet"),
+// and ~image reverses the order (a maximum of ~image is a minimum)
+__device__ __forceinline__ uint32_t f2ord(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
+__device__ __forceinline__ unsigned long long d2ord(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ord2d(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
+}
 #endif
 // pointer sets of the BatchNorm apply passes; a launch takes two and its workgroups pick by blockIdx.y (twin launches as above)
 struct BnFwdPtrs {

@@ -38,13 +38,6 @@ struct GridPlan {  // per cloud, written by gs_mark_kernel
   int32_t r;       // stage-B picks
 };
 
-// order-preserving image of a float in uint32, and back
-__device__ __forceinline__ uint32_t f2ord(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
-
 // the rows of cloud s that are sampled: n > m of a cloud whose status is OK, else 0 (uniform over the workgroup)
 __device__ __forceinline__ int sampled_rows(const int32_t* counts, const int32_t* status, int s, int m, int64_t n_bound) {
   const int n = (int)min((int64_t)max(counts[s], 0), n_bound);

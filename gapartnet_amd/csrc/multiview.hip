@@ -13,32 +13,27 @@
 //            the arg-max of the pairs still eligible (exact 64-bit cross products), one union, at most GT - 1 rounds; a listed pair
 //            refused for its clusters is struck from the list, since clusters only grow
 //   relabel  fused_inst = fused_of[part_of]
-//   gather   the stable multi-way partition of articulate.hip over 9-bit keys (the fused id of a pixel): per-chunk per-part counts,
-//            one scan over (view, chunk) per part, ordered stores.  Not shared with gpn_parts_gather through a header: that one
-//            holds 64-wide tables and 6-bit ballots in LDS per frame, this one 512-wide tables over all views.
+//   gather   the stable multi-way partition of pixel_parts.h over 9-bit keys (the fused id of a pixel): counts [F][V][chunk], one
+//            scan over (view, chunk) per fused part, a member's world row, its NPCS and its pixel stored
+// The wave helpers (wave_hist_add, wave_match), the partition and the workgroup arg-max (block_best) are pixel_parts.h's, shared with
+// articulate.hip: that file's policy holds 64-wide tables and 6-bit ballots per frame, this one's 512-wide tables over all views.
 // No float atomics; integer atomics only on minima, histograms and counters (order-free); no host read; every result is
 // independent of timing.
-#include "gpn_common.h"  // first: pulls <cstring> ahead of the HIP/rocPRIM headers
+#include "pixel_parts.h"  // first: gpn_common.h pulls <cstring> ahead of the HIP/rocPRIM headers
 
 #include <algorithm>
 
 #include <rocprim/rocprim.hpp>
 
-#include "wg_scan.h"
-
 namespace {
 
 using namespace gpn;
+using namespace gpn::pp;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;  // pixels per thread: pixel = chunk * kChunk + e * kThreads + tid
-constexpr int kChunk = kThreads * kPer;
 constexpr int kMaxV = GPN_VIEWS_MAX;
 constexpr int kMaxG = GPN_FUSE_PARTS_MAX;
-constexpr int kGroupRounds = 8;         // key groups a wave resolves by ballots before its remaining lanes add one by one
 constexpr uint64_t kDeadKey = ~0ull;    // a pixel outside the occupancy
-constexpr unsigned kKeyBits = 40;       // 30 voxel bits, 9 part bits, and the bit that sorts the dead key last
+constexpr unsigned kSortBits = 40;      // 30 voxel bits, 9 part bits, and the bit that sorts the dead key last
 constexpr int kGridCells = 1024;        // cells per axis
 constexpr int kLdsPartsMax = 128;       // GT * GT * 4 <= 64 KiB
 constexpr int kMergeThreads = 1024;
@@ -46,20 +41,6 @@ constexpr int kMergeWaves = kMergeThreads / 64;
 constexpr int kMergeList = 3072;  // statically eligible pairs the merge keeps in LDS
 
 int g_lds_parts = kLdsPartsMax;  // the pair table is summed in LDS for GT <= this
-
-// order-preserving image of a float in uint32 / of a double in uint64, and back
-__device__ __forceinline__ uint32_t f2ord(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
-__device__ __forceinline__ unsigned long long d2ord(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ord2d(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
 
 // the live parts of view v and the global id of its part 0 (workgroup-uniform; contains a barrier)
 __device__ __forceinline__ int view_base(const int32_t* __restrict__ n_parts, int v, int GT, int* sh) {
@@ -71,32 +52,6 @@ __device__ __forceinline__ int view_base(const int32_t* __restrict__ n_parts, in
   }
   __syncthreads();
   return *sh;
-}
-
-// bins[key] += 1 for every lane with key >= 0, one LDS atomic per group of equal keys.  Called by whole waves.
-__device__ __forceinline__ void wave_hist_add(int* bins, int key) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(key >= 0);
-  for (int round = 0; todo != 0ull && round < kGroupRounds; ++round) {  // (todo is wave-uniform)
-    const int lead = __ffsll((long long)todo) - 1;
-    const int k = __shfl(key, lead, 64);
-    const unsigned long long same = __ballot(key == k);
-    if (lane == lead) atomicAdd(&bins[k], __popcll(same));
-    todo &= ~same;
-  }
-  if ((todo >> lane) & 1ull) atomicAdd(&bins[key], 1);
-}
-
-// the lanes of the wave whose key (0 .. 511, `ok` lanes only) equals this lane's: ten ballots.  0 for a lane that is not ok.
-__device__ __forceinline__ unsigned long long wave_match9(int key, bool ok) {
-  unsigned long long same = __ballot(ok);
-#pragma unroll
-  for (int b = 0; b < 9; ++b) {
-    const bool bit = ((key >> b) & 1) != 0;
-    const unsigned long long m = __ballot(ok && bit);
-    same &= bit ? m : ~m;
-  }
-  return ok ? same : 0ull;
 }
 
 // ---- 1. world rows, part_of, areas, bounds ------------------------------------------------------------------------------------------
@@ -248,18 +203,7 @@ __global__ __launch_bounds__(kThreads) void mv_tables_kernel(const uint64_t* __r
 }
 
 // ---- 4. merge -----------------------------------------------------------------------------------------------------------------------
-struct Cand {
-  int inter, mv, e;  // e = g << 9 | h with g < h, -1 = none
-};
-// a before b: the larger inter / min(vol) by 64-bit cross-multiplication, ties to the smaller (g, h)
-__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
-  if (a.e < 0) return false;
-  if (b.e < 0) return true;
-  const long long l = (long long)a.inter * b.mv, r = (long long)b.inter * a.mv;
-  if (l != r) return l > r;
-  return a.e < b.e;
-}
-
+// a candidate: num = inter, den = min(vol), e = g << 9 | h with g < h.  The larger ratio first, ties to the smaller (g, h).
 __global__ __launch_bounds__(kMergeThreads) void mv_merge_kernel(
     const int32_t* __restrict__ inter, const int32_t* __restrict__ vol, const int32_t* __restrict__ cls,
     const int32_t* __restrict__ n_parts, int V, int GT, int min_inter, double min_overlap, int32_t* __restrict__ fused_of,
@@ -268,8 +212,7 @@ __global__ __launch_bounds__(kMergeThreads) void mv_merge_kernel(
   __shared__ int rep[kMaxG], svol[kMaxG], cvol[kMaxG], scls[kMaxG], sview[kMaxG], isrep[kMaxG], frep[kMaxG], fidx[kMaxG];
   __shared__ int sbase[kMaxV + 1];
   __shared__ unsigned long long cviews[kMaxG];
-  __shared__ Cand wbest[kMergeWaves];
-  __shared__ Cand won;
+  __shared__ RatioCand wbest[kMergeWaves];
   __shared__ int list_e[kMergeList], list_c[kMergeList];  // the statically eligible pairs: e (-1: struck) and inter
   __shared__ int n_list;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -317,8 +260,8 @@ __global__ __launch_bounds__(kMergeThreads) void mv_merge_kernel(
   const int nc = n_list;
   const bool listed = nc <= kMergeList;
   int nl = 0;
-  for (int round = 0; round < GT; ++round) {  // (workgroup-uniform: the exit below is read from LDS by every thread)
-    Cand best{0, 1, -1};
+  for (int round = 0; round < GT; ++round) {  // (workgroup-uniform: block_best hands every thread the same winner)
+    RatioCand best{0, 1, -1};
     if (listed) {
       for (int i = tid; i < nc; i += kMergeThreads) {  // (entry i is always this thread's)
         const int e = list_e[i];
@@ -329,8 +272,8 @@ __global__ __launch_bounds__(kMergeThreads) void mv_merge_kernel(
           list_e[i] = -1;  // refused for good: clusters only grow
           continue;
         }
-        const Cand cand{list_c[i], min(svol[g], svol[hh]), e};
-        if (cand_better(cand, best)) best = cand;
+        const RatioCand cand{list_c[i], min(svol[g], svol[hh]), e};
+        if (ratio_better(cand, best)) best = cand;
       }
     } else {
       for (int g = wave; g < GT; g += kMergeWaves) {
@@ -342,41 +285,24 @@ __global__ __launch_bounds__(kMergeThreads) void mv_merge_kernel(
           if (!static_ok(g, hh, c)) continue;
           const int rh = rep[hh];
           if (rh == rg || (cviews[rh] & mg) != 0ull) continue;
-          const Cand cand{c, min(svol[g], svol[hh]), (g << 9) | hh};
-          if (cand_better(cand, best)) best = cand;
+          const RatioCand cand{c, min(svol[g], svol[hh]), (g << 9) | hh};
+          if (ratio_better(cand, best)) best = cand;
         }
       }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      Cand o;
-      o.inter = __shfl_xor(best.inter, off, 64);
-      o.mv = __shfl_xor(best.mv, off, 64);
-      o.e = __shfl_xor(best.e, off, 64);
-      if (cand_better(o, best)) best = o;
-    }
-    if (lane == 0) wbest[wave] = best;
-    __syncthreads();
-    if (tid == 0) {
-      Cand bb = wbest[0];
-      for (int w = 1; w < kMergeWaves; ++w)
-        if (cand_better(wbest[w], bb)) bb = wbest[w];
-      won = bb;
-    }
-    __syncthreads();
-    const Cand w = won;
+    const RatioCand w = block_best<kMergeWaves>(best, wbest);
     if (w.e < 0) break;
     const int g = w.e >> 9, hh = w.e & 511;
     const int ra = rep[g], rb = rep[hh];
     const int keep = min(ra, rb), gone = max(ra, rb);
-    __syncthreads();  // every thread has read rep and won
+    __syncthreads();  // every thread has read rep
     if (tid < GT && rep[tid] == gone) rep[tid] = keep;
     if (tid == 0) {
       cviews[keep] |= cviews[gone];
       cvol[keep] += cvol[gone];
       links[nl * 3 + 0] = g;
       links[nl * 3 + 1] = hh;
-      links[nl * 3 + 2] = w.inter;
+      links[nl * 3 + 2] = w.num;
     }
     ++nl;
     __syncthreads();
@@ -422,73 +348,33 @@ __global__ __launch_bounds__(kThreads) void mv_relabel_kernel(const int32_t* __r
   fused_inst[i] = (g >= 0 && g < GT) ? fused_of[g] : -1;
 }
 
-__device__ __forceinline__ int fused_key(const int32_t* __restrict__ fused_inst, int64_t g, bool inside, int F) {
-  if (!inside) return -1;
-  const int f = fused_inst[g];
-  return (f >= 0 && f < F) ? f : -1;
-}
-
-// per chunk: the members of every fused part.  counts [F][V][nchunk]
-__global__ __launch_bounds__(kThreads) void mv_count_kernel(const int32_t* __restrict__ fused_inst, int64_t HW, int F,
-                                                            int32_t* __restrict__ counts) {
-  __shared__ int h[kMaxG];
-  const int v = blockIdx.y, tid = threadIdx.x;
-  for (int i = tid; i < kMaxG; i += kThreads) h[i] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-    const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
-    wave_hist_add(h, fused_key(fused_inst, (int64_t)v * HW + p, p < HW, F));
+// the partition's policy: key = the fused part of a pixel; counts [F][V][nchunk], one scan per fused part over its V * nchunk cells;
+// a member's world row and NPCS as float64, and its pixel
+struct MvParts {
+  static constexpr int kMaxKeys = kMaxG, kKeyBits = 9;
+  const float* wrows;
+  const float* npcs;
+  const int32_t* fused_inst;
+  const int64_t* seg_start;
+  int F;
+  int64_t n_total;
+  double* xyz;
+  double* npcs_out;
+  int64_t* src;
+  __device__ int live_keys(int) const { return F; }
+  __device__ int key(int, int64_t g, bool inside) const {
+    if (!inside) return -1;
+    const int f = fused_inst[g];
+    return (f >= 0 && f < F) ? f : -1;
   }
-  __syncthreads();
-  for (int f = tid; f < F; f += kThreads) counts[((int64_t)f * gridDim.y + v) * gridDim.x + blockIdx.x] = h[f];
-}
-
-// one workgroup per fused part: the counts of its (view, chunk) cells -> their exclusive prefix, in place
-__global__ __launch_bounds__(kThreads) void mv_scan_kernel(int32_t* __restrict__ counts, int64_t ncell) {
-  __shared__ int wsum[kWaves];
-  int32_t* c = counts + (int64_t)blockIdx.x * ncell;
-  block_scan_tiled<kWaves, int>(ncell, [&](int64_t i) { return c[i]; }, c, wsum);
-}
-
-__global__ __launch_bounds__(kThreads) void mv_store_kernel(const float* __restrict__ wrows, const float* __restrict__ npcs,
-                                                            const int32_t* __restrict__ fused_inst,
-                                                            const int64_t* __restrict__ seg_start, const int32_t* __restrict__ base,
-                                                            int64_t HW, int F, int64_t n_total, double* __restrict__ xyz,
-                                                            double* __restrict__ npcs_out, int64_t* __restrict__ src) {
-  __shared__ int cnt[kPer * kWaves][kMaxG];  // members of a part in (slot e, wave), then the members before that (slot, wave)
-  const int v = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int i = tid; i < kPer * kWaves * kMaxG; i += kThreads) (&cnt[0][0])[i] = 0;
-  __syncthreads();
-  int key[kPer], rank[kPer];
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-    const int64_t p = (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
-    key[e] = fused_key(fused_inst, (int64_t)v * HW + p, p < HW, F);
-    const unsigned long long same = wave_match9(key[e], key[e] >= 0);
-    rank[e] = __popcll(same & below);
-    if (key[e] >= 0 && rank[e] == 0) cnt[e * kWaves + wave][key[e]] = __popcll(same);  // (the group's lowest lane)
-  }
-  __syncthreads();
-  for (int f = tid; f < F; f += kThreads) {  // (slot order: e first, then the wave)
-    int run = base[((int64_t)f * gridDim.y + v) * gridDim.x + blockIdx.x];
-#pragma unroll
-    for (int s = 0; s < kPer * kWaves; ++s) {
-      const int c = cnt[s][f];
-      cnt[s][f] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < kPer; ++e) {
-    if (key[e] < 0) continue;
-    const int64_t s0 = seg_start[key[e]];
-    if (s0 < 0) continue;
-    const int64_t pos = s0 + cnt[e * kWaves + wave][key[e]] + rank[e];
-    if (pos >= n_total) continue;
-    const int64_t g = (int64_t)v * HW + (int64_t)blockIdx.x * kChunk + e * kThreads + tid;
+  __device__ int64_t counts_index(int v, int key, int chunk, int nchunk, int V) const { return ((int64_t)key * V + v) * nchunk + chunk; }
+  dim3 scan_grid(int) const { return dim3((unsigned)F); }
+  int64_t scan_len(int V, int64_t nchunk) const { return (int64_t)V * nchunk; }
+  __device__ void store(int, int key, int rank, int64_t g) const {
+    const int64_t s0 = seg_start[key];
+    if (s0 < 0) return;
+    const int64_t pos = s0 + rank;
+    if (pos >= n_total) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       xyz[pos * 3 + k] = (double)wrows[g * 3 + k];
@@ -496,7 +382,7 @@ __global__ __launch_bounds__(kThreads) void mv_store_kernel(const float* __restr
     }
     src[pos] = g;
   }
-}
+};
 
 inline bool views_ok(int V, int H, int W) {
   return V >= 0 && V <= kMaxV && H >= 1 && H <= 16384 && W >= 1 && W <= 16384 &&
@@ -517,7 +403,7 @@ OverlapWs overlap_ws(void* ws, size_t N) {
   o.uniq = w.take<uint64_t>(N);
   o.n_uniq = w.take<unsigned int>(1);
   size_t a = 0, b = 0;
-  (void)rocprim::radix_sort_keys(nullptr, a, (const uint64_t*)nullptr, (uint64_t*)nullptr, N, 0u, kKeyBits, (hipStream_t) nullptr);
+  (void)rocprim::radix_sort_keys(nullptr, a, (const uint64_t*)nullptr, (uint64_t*)nullptr, N, 0u, kSortBits, (hipStream_t) nullptr);
   (void)rocprim::unique(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned int*)nullptr, N,
                         rocprim::equal_to<uint64_t>(), (hipStream_t) nullptr);
   o.prim_bytes = a > b ? a : b;
@@ -587,7 +473,7 @@ extern "C" int gpn_views_overlap(const float* wrows, const int32_t* part_of, con
   hipLaunchKernelGGL(mv_keys_kernel, grid, dim3(kThreads), 0, stream, wrows, part_of, lo, cell, HW, GT, o.keys, keys_out, dropped);
   GPN_CHECK_LAUNCH();
   size_t tmp = o.prim_bytes;
-  GPN_CHECK_HIP(rocprim::radix_sort_keys(o.prim, tmp, (const uint64_t*)o.keys, o.sorted, N, 0u, kKeyBits, stream));
+  GPN_CHECK_HIP(rocprim::radix_sort_keys(o.prim, tmp, (const uint64_t*)o.keys, o.sorted, N, 0u, kSortBits, stream));
   tmp = o.prim_bytes;
   GPN_CHECK_HIP(rocprim::unique(o.prim, tmp, (const uint64_t*)o.sorted, o.uniq, o.n_uniq, N, rocprim::equal_to<uint64_t>(), stream));
   const bool lds = GT <= g_lds_parts;
@@ -650,13 +536,5 @@ extern "C" int gpn_views_gather(const float* wrows, const float* npcs, const int
   gpn::WsCarver carve(ws, ws_bytes);
   int32_t* counts = carve.take<int32_t>((size_t)F * V * nchunk);
   GPN_CHECK_WS(carve);
-  const dim3 grid((unsigned)nchunk, (unsigned)V);
-  hipLaunchKernelGGL(mv_count_kernel, grid, dim3(kThreads), 0, stream, fused_inst, HW, F, counts);
-  GPN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mv_scan_kernel, dim3((unsigned)F), dim3(kThreads), 0, stream, counts, (int64_t)V * nchunk);
-  GPN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mv_store_kernel, grid, dim3(kThreads), 0, stream, wrows, npcs, fused_inst, seg_start, counts, HW, F, n_total, xyz,
-                     npcs_out, src);
-  GPN_CHECK_LAUNCH();
-  return GPN_OK;
+  return pp_partition(MvParts{wrows, npcs, fused_inst, seg_start, F, n_total, xyz, npcs_out, src}, V, HW, counts, stream);
 }

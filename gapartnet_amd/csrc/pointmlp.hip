@@ -70,11 +70,6 @@ __device__ __forceinline__ bool find_tile(const int64_t* __restrict__ off, int S
   return false;
 }
 
-__device__ __forceinline__ int ordered_key(float v) {  // monotone float -> int (its own inverse)
-  const int i = __float_as_int(v);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-
 struct FwdArgs {
   XView x;
   const float* W;
@@ -217,18 +212,18 @@ __global__ __launch_bounds__(kThreads) void pointmlp_fwd_kernel(const FwdArgs a)
       mx = o > mx ? o : mx;
       o = __shfl_xor(mx, 32);
       mx = o > mx ? o : mx;
-      if (q == 0 && col_ok && mx > -INFINITY) atomicMax(&a.M[(int64_t)g.s * a.cout + col], ordered_key(mx));
+      if (q == 0 && col_ok && mx > -INFINITY) atomicMax(&a.M[(int64_t)g.s * a.cout + col], gpn::float_order(mx));
     }
   }
 }
 
 __global__ void max_init_kernel(int* __restrict__ M, int64_t n) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) M[e] = ordered_key(-INFINITY);
+  if (e < n) M[e] = gpn::float_order(-INFINITY);
 }
 __global__ void max_decode_kernel(int* __restrict__ M, int64_t n) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) M[e] = M[e] >= 0 ? M[e] : M[e] ^ 0x7fffffff;  // (the key map is its own inverse: M now holds the floats' bits)
+  if (e < n) M[e] = __float_as_int(gpn::order_float(M[e]));  // (M now holds the floats' bits)
 }
 
 // ---- wgrad -------------------------------------------------------------------------------------------------------------------

@@ -27,18 +27,13 @@ constexpr int kSplit = 16;          // workgroups per scene in sp_points_kernel
 constexpr int kIdsThreads = 1024, kThreads = 256;
 constexpr double kFix = 4294967296.0;  // 2^32
 
-__device__ __forceinline__ uint32_t order_bits(float v) {  // monotone float -> unsigned
-  const uint32_t b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float order_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+using gpn::f2ord;
+using gpn::ord2f;
 
 // statistics of one (scene, instance) slot
 struct SlotStats {
   unsigned long long sum[3];  // fixed point, two's complement
-  uint32_t lo[3], hi[3];      // order_bits
+  uint32_t lo[3], hi[3];      // f2ord images
   uint32_t count;
   int32_t first;              // smallest point row (batch-wide)
 };
@@ -156,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void sp_points_kernel(const float* __rest
       atomicMin(&s_first[slot], (int32_t)p);
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const uint32_t k = order_bits(q[j]);
+        const uint32_t k = f2ord(q[j]);
         atomicMin(&s_lo[3 * slot + j], k);
         atomicMax(&s_hi[3 * slot + j], k);
         atomicAdd(&s_sum[3 * slot + j], (unsigned long long)(long long)__double2ll_rn((double)q[j] * kFix));
@@ -198,8 +193,8 @@ __global__ __launch_bounds__(kThreads) void sp_finish_kernel(const int32_t* __re
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       r[j] = (float)(((double)(long long)g.sum[j] / kFix) / (double)g.count);
-      r[3 + j] = order_float(g.lo[j]);
-      r[6 + j] = order_float(g.hi[j]);
+      r[3 + j] = ord2f(g.lo[j]);
+      r[6 + j] = ord2f(g.hi[j]);
     }
   } else {
 #pragma unroll

@@ -644,11 +644,8 @@ __global__ __launch_bounds__(256) void voxb_sort_kernel(const int32_t* __restric
 // (min / max are exact: any order gives the same bits), the LAST workgroup to finish - a ticket - applies the reference's
 // -1e-4 / +1e-4 margins and derives the batch's cell grid (voxb_extent_kernel's arithmetic).
 constexpr int kRangeSplit = 32;
-__device__ __forceinline__ int float_order(float f) {  // monotone map float -> int (for atomicMin / atomicMax)
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float order_float(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+using gpn::float_order;
+using gpn::order_float;
 
 __global__ void voxb_range_init_kernel(int* __restrict__ lo_bits, int* __restrict__ hi_bits, unsigned* __restrict__ ticket, int64_t n) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

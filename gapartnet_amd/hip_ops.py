@@ -2064,14 +2064,15 @@ def joint_from_rigid(rotation, translation, norm, joint_type="revolute"):
 PARTS_MAX = 64
 
 
-def _part_maps(inst, valid, what):
-    """inst [V,H,W] i32 / i64 (FramePrediction.instance is i64) and valid [V,H,W] u8 / bool -> contiguous i32 / u8"""
+def _part_maps(inst, valid, what, top=PARTS_MAX):
+    """inst [V,H,W] i32 / i64 (FramePrediction.instance is i64) and valid [V,H,W] u8 / bool -> contiguous i32 / u8; ``top``: the
+    table's widest (a wider integer type is clamped to -1 .. top before the cast)"""
     V, H, W = _frame_dims(inst)
     if inst.dtype != torch.int32:
         if inst.dtype not in (torch.int64, torch.int16, torch.int8, torch.uint8):
             raise _C.GpnError(f"{what}: an instance map is an integer tensor, got {inst.dtype}")
-        # (every value outside 0 .. 63 belongs to no part; a plain cast of an int64 would wrap, and so would -1 in an unsigned clamp)
-        inst = inst.to(torch.int64).clamp(-1, PARTS_MAX).to(torch.int32)
+        # (every value outside 0 .. top - 1 belongs to no part; a plain cast of an int64 would wrap, and so would -1 in an unsigned clamp)
+        inst = inst.to(torch.int64).clamp(-1, top).to(torch.int32)
     if tuple(valid.shape) != (V, H, W):
         raise _C.GpnError(f"{what}: valid must be [V,H,W] like the instance map")
     return inst.contiguous(), _c(valid, torch.uint8), V, H, W
@@ -2203,14 +2204,12 @@ def views_world(rows, valid, inst, n_parts, R, t, GT):
     (flip = 0), inst [V,H,W] i32 / i64, n_parts [V], R [V,3,3], t [V,3] f64 (a camera point is (world - t) @ R), GT = the table
     width -> (wrows [V*H*W,3] f32, part_of [V,H,W] i32, area [GT] i32, lo [3] f64) on the device"""
     dev = _dev(rows, valid, inst, R, t)
-    V, H, W = _view_dims(inst, "views_world")
+    _view_dims(inst, "views_world")
     GT = _fuse_width(GT, "views_world")
-    if inst.dtype != torch.int32:  # (every value outside 0 .. 511 belongs to no part; a plain cast of an int64 would wrap)
-        inst = inst.to(torch.int64).clamp(-1, FUSE_PARTS_MAX).to(torch.int32)
-    inst, valid, rows = inst.contiguous(), _c(valid, torch.uint8), _c(rows, torch.float32)
-    R, t = _c(R, torch.float64), _c(t, torch.float64)
-    if tuple(valid.shape) != (V, H, W) or rows.numel() != V * H * W * 6 or R.numel() != V * 9 or t.numel() != V * 3:
-        raise _C.GpnError("views_world: valid [V,H,W], one row per pixel, R [V,3,3] and t [V,3]")
+    inst, valid, V, H, W = _part_maps(inst, valid, "views_world", FUSE_PARTS_MAX)
+    rows, R, t = _c(rows, torch.float32), _c(R, torch.float64), _c(t, torch.float64)
+    if rows.numel() != V * H * W * 6 or R.numel() != V * 9 or t.numel() != V * 3:
+        raise _C.GpnError("views_world: one row per pixel, R [V,3,3] and t [V,3]")
     n_parts = _part_counts(n_parts, V, dev, "views_world")
     wrows = torch.empty((V * H * W, 3), dtype=torch.float32, device=dev)
     part_of = torch.empty((V, H, W), dtype=torch.int32, device=dev)

@@ -315,13 +315,14 @@ def _backproject_numpy(depth, rgb, K, keep, depth_scale, flip):
 
 
 def _check_frames(depth, rgb, K, keep):
-    depth, rgb = torch.as_tensor(depth), torch.as_tensor(rgb)
+    """``rgb`` None: frames without colours (``backproject_frames`` takes them as black)"""
+    depth, rgb = torch.as_tensor(depth), None if rgb is None else torch.as_tensor(rgb)
     if depth.dim() == 2:
-        depth, rgb = depth[None], rgb[None]
+        depth, rgb = depth[None], None if rgb is None else rgb[None]
     if depth.dim() != 3 or depth.dtype not in (torch.float32, torch.float64, torch.uint16, torch.int16):
         raise ValueError("depth must be [V, H, W] (or [H, W]) float32, float64 or uint16")
     V, H, W = (int(v) for v in depth.shape)
-    if tuple(rgb.shape) != (V, H, W, 3) or rgb.dtype != torch.uint8:
+    if rgb is not None and (tuple(rgb.shape) != (V, H, W, 3) or rgb.dtype != torch.uint8):
         raise ValueError(f"rgb must be uint8 [{V}, {H}, {W}, 3]")
     K = torch.as_tensor(K).detach().cpu().double()  # (host data: the overlay's camera is read from it)
     if K.numel() == 9:
@@ -333,6 +334,26 @@ def _check_frames(depth, rgb, K, keep):
         if tuple(keep.shape) != (V, H, W):
             raise ValueError(f"keep must be [{V}, {H}, {W}]")
     return depth, rgb, K, keep
+
+
+def backproject_frames(depth, rgb, K, keep, depth_scale, flip):
+    """section FR's back-projection of frames that passed ``_check_frames``, on whichever device they live on; ``rgb`` None: black.
+    -> (rows [V*H*W, 6] f32, valid [V,H,W] u8, counts [V] = the valid pixels of every frame) on the frames' device.  No host read."""
+    V, H, W = (int(v) for v in depth.shape)
+    dev = depth.device
+    if rgb is None:
+        rgb = torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev)
+    if depth.is_cuda:
+        from . import backend
+        hip = backend.raw()
+        if hip.name != "hip":
+            raise RuntimeError("backproject_frames on GPU tensors needs the HIP library as the operator backend")
+        return hip.frame_backproject(depth, rgb, K.to(dev, non_blocking=True), keep, depth_scale, flip)
+    d = depth.numpy()
+    rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), K.numpy(),
+                                     None if keep is None else keep.numpy(), depth_scale, flip)
+    valid = torch.from_numpy(valid.reshape(V, H, W).astype(np.uint8))
+    return torch.from_numpy(rows), valid, valid.sum((1, 2))
 
 
 # ---------------------------------------------------------------------------------------------------- object isolation
@@ -528,15 +549,13 @@ def _isolate_checked(depth, K, keep, seeds, depth_scale, flip, cfg: IsolateConfi
         if hip.name != "hip":
             raise RuntimeError("isolate_objects on GPU tensors needs the HIP library as the operator backend")
         dev = depth.device
-        rgb = torch.zeros((V, H, W, 3), dtype=torch.uint8, device=dev)  # (the rows' colours are not read here)
-        rows, valid, valid_counts = hip.frame_backproject(depth, rgb, K.to(dev, non_blocking=True), keep, depth_scale, flip)
+        rows, valid, valid_counts = backproject_frames(depth, None, K, keep, depth_scale, flip)  # (the rows' colours are not read here)
         got = hip.frame_isolate(rows, valid, valid_counts, seeds, cfg.max_planes, cfg.n_hyp, cfg.tol, cfg.min_plane_fraction, cfg.z_min,
                                 cfg.z_max, cfg.jump_abs, cfg.jump_rel, cfg.select, cfg.min_pixels,
                                 torch.from_numpy(anchor).to(dev, non_blocking=True) if cfg.select == "center" else None)
         return ObjectIsolation(*(got[f] for f in ("keep", "labels", "sizes", "planes", "plane_inliers", "n_planes", "chosen", "status")))
-    d = depth.numpy()
-    rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, np.zeros((V, H, W, 3), dtype=np.uint8), K.numpy(),
-                                     None if keep is None else keep.numpy(), depth_scale, flip)
+    rows, valid, _ = backproject_frames(depth, None, K, keep, depth_scale, flip)
+    rows, valid = rows.numpy(), valid.numpy().reshape(V, H * W) != 0
     per = [_isolate_frame_numpy(rows[v * H * W:(v + 1) * H * W, :3], valid[v], H, W, seeds[v], cfg, anchor[v]) for v in range(V)]
     col = lambda i, dt: torch.from_numpy(np.stack([np.asarray(p[i]) for p in per]).astype(dt)) if V else torch.zeros((0,), dtype=torch.int32)  # noqa: E731
     return ObjectIsolation(keep=col(0, np.uint8).reshape(V, H, W), labels=col(1, np.int32).reshape(V, H, W), sizes=col(2, np.int32).reshape(V, H * W),
@@ -552,11 +571,8 @@ def isolate_objects(depth, K, depth_scale: float = 1.0, flip: bool = False, keep
     ``depth_scale``, ``flip``, ``seed`` as in ``prepare_frames``.  The result's ``keep`` is what ``prepare_frames(keep=)`` takes; no
     host read is made.  CPU tensors take the same contract in numpy / scipy."""
     cfg = IsolateConfig() if config is None else config
-    depth = torch.as_tensor(depth)
-    H, W = int(depth.shape[-2]), int(depth.shape[-1])
-    V = 1 if depth.dim() == 2 else int(depth.shape[0])
-    depth, _, K, keep = _check_frames(depth, torch.zeros((V, H, W, 3) if depth.dim() == 3 else (H, W, 3), dtype=torch.uint8), K, keep)
-    return _isolate_checked(depth, K, keep, _frame_seeds(seed, V), depth_scale, flip, cfg)
+    depth, _, K, keep = _check_frames(depth, None, K, keep)
+    return _isolate_checked(depth, K, keep, _frame_seeds(seed, int(depth.shape[0])), depth_scale, flip, cfg)
 
 
 def prepare_frames(depth, rgb, K, num_points: int = 20000, presample: int = 4, seed=0, keep=None, depth_scale: float = 1.0,
@@ -602,17 +618,16 @@ def _prepare_checked_frames(depth, rgb, K, keep, num_points, presample, seed, de
         got = hip.frame_prepare(depth, rgb, K.to(depth.device, non_blocking=True), m, cap, seeds, keep=keep, depth_scale=depth_scale, flip=flip,
                                 hash_bits=hash_bits, max_groups=max_groups, sampler=sampler)
         return _prepared_from_tables(got, m, offsets, got["rows"])
-    d = depth.numpy()
-    rows, valid = _backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), K.numpy(),
-                                     None if keep is None else keep.numpy(), depth_scale, flip)
+    rows, valid, _ = backproject_frames(depth, rgb, K, keep, depth_scale, flip)
+    valid = valid.numpy().reshape(V, H * W)
     parts = []
     for v in range(V):
-        frame = rows[offsets[v]:offsets[v + 1]].copy()
+        frame = rows[offsets[v]:offsets[v + 1]].numpy().copy()
         drop = np.ones(H * W, dtype=bool)
         drop[select_pixels(np.nonzero(valid[v])[0], seeds[v], cap, hash_bits)] = False
         frame[drop, :3] = np.nan
         parts.append(_prepare_cloud_torch(torch.from_numpy(frame), m, sampler, seeds[v]))
-    return _prepared_from_parts(parts, offsets, torch.from_numpy(rows), sampler)
+    return _prepared_from_parts(parts, offsets, rows, sampler)
 
 
 # the box edges of draw_bbox (structure/utils.py:73-89; include/gpn.h section VS): (corner a, corner b, colour as written, thickness)
@@ -839,6 +854,12 @@ class PartPredictor:
     def __init__(self, model, num_points: int = 20000, max_iters: int = 100, sampler: str = "fps"):
         self.model, self.num_points, self.max_iters = model.eval(), int(num_points), int(max_iters)
         self.sampler = _check_sampler(sampler)  # "grid": the opt-in octree-cell sampler (clouds take the seeds 0, 1, ...)
+
+    def with_sampler(self, sampler: Optional[str]) -> "PartPredictor":
+        """this predictor, or one of the same model and settings with another ``sampler`` (None: keep this one's)"""
+        if sampler is None or sampler == self.sampler:
+            return self
+        return type(self)(self.model, num_points=self.num_points, max_iters=self.max_iters, sampler=sampler)
 
     def _empty(self, n: int, C: int, status: int, scale, dev) -> PartPrediction:
         i64, f32 = torch.int64, torch.float32

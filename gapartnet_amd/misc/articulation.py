@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import info
-from .joint_fitting import JointLeg, _need_hip, draw_joint, estimate_joints_packed, joint_from_rigid
+from .joint_fitting import JointLeg, _lists, _maps, _need_hip, draw_joint, estimate_joints_packed, joint_from_rigid
 
 PARTS_MAX = 64  # GPN_PARTS_MAX
 FIXED, REVOLUTE, PRISMATIC = "fixed", "revolute", "prismatic"
@@ -92,34 +92,6 @@ class Articulation:
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
-def _maps(inst, what: str) -> torch.Tensor:
-    """[V,H,W] (or [H,W], or a sequence of [H,W]) integer tensor"""
-    if not torch.is_tensor(inst) and len(inst) > 0 and torch.is_tensor(inst[0]):
-        inst = torch.stack(list(inst))
-    inst = torch.as_tensor(inst)
-    if inst.dim() == 2:
-        inst = inst[None]
-    if inst.dim() != 3 or inst.dtype.is_floating_point or inst.dtype == torch.bool:
-        raise ValueError(f"{what} must be an integer [V,H,W] (or [H,W]) map")
-    return inst
-
-
-def _class_lists(classes, V: int, what: str) -> list:
-    """one 1-D class list per frame; a single frame may pass its list bare"""
-    if torch.is_tensor(classes) or isinstance(classes, np.ndarray):
-        classes = [classes] if classes.ndim == 1 else list(classes)
-    classes = list(classes)
-    if V == 1 and all(np.ndim(c) == 0 for c in classes):  # (a flat list of class ids, the empty one included)
-        classes = [classes]
-    if len(classes) != V:
-        raise ValueError(f"{what}: {V} frames need {V} class lists, got {len(classes)}")
-    out = [c.reshape(-1) if torch.is_tensor(c) else torch.as_tensor(np.asarray(c, dtype=np.int64).reshape(-1)) for c in classes]
-    for c in out:
-        if int(c.shape[0]) > PARTS_MAX:
-            raise ValueError(f"{what}: at most {PARTS_MAX} parts a frame, got {int(c.shape[0])}")
-    return out
-
-
 def _class_table(classes: list, P: int, dev) -> torch.Tensor:
     """[V,P] i32 on ``dev``, -1 beyond a list's end; device lists are padded on the device (no host read)"""
     table = torch.full((len(classes), P), -1, dtype=torch.int32, device=dev)
@@ -219,7 +191,7 @@ def _checked_maps(inst_a, inst_b, classes_a, classes_b, valid_a, valid_b):
     if inst_a.shape != inst_b.shape or inst_a.device != inst_b.device:
         raise ValueError("both frames of a pair have one size and live on one device")
     V = int(inst_a.shape[0])
-    cls_a, cls_b = _class_lists(classes_a, V, "classes_a"), _class_lists(classes_b, V, "classes_b")
+    cls_a, cls_b = _lists(classes_a, V, "classes_a", PARTS_MAX), _lists(classes_b, V, "classes_b", PARTS_MAX)
     valid = []
     for inst, val in ((inst_a, valid_a), (inst_b, valid_b)):
         val = (inst >= 0) if val is None else torch.as_tensor(val).reshape(inst.shape).to(inst.device)
@@ -262,33 +234,17 @@ def articulation_from_maps(depth_a, depth_b, K, inst_a, inst_b, classes_a, class
     place in A.  On the GPU: ONE host read (the match and area tables) in
     front of the joint pass."""
     from .. import inference
-    sides = []
-    for depth in (depth_a, depth_b):
-        depth = torch.as_tensor(depth)
-        rgb = torch.zeros(tuple(depth.shape) + (3,), dtype=torch.uint8, device=depth.device)  # (the frame path takes colours along)
-        sides.append(inference._check_frames(depth, rgb, K, None)[:3])
-    (da, rgb_a, Kc), (db, rgb_b, _) = sides
+    (da, _, Kc, _), (db, _, _, _) = (inference._check_frames(d, None, K, None) for d in (depth_a, depth_b))
     inst_a, inst_b = _maps(inst_a, "inst_a"), _maps(inst_b, "inst_b")
     if not (da.shape == db.shape == inst_a.shape == inst_b.shape) or len({t.device for t in (da, db, inst_a, inst_b)}) != 1:
         raise ValueError("the depth frames and instance maps of both sides have one shape and live on one device")
     V, H, W = (int(v) for v in da.shape)
     dev = da.device
-    cls_a, cls_b = _class_lists(classes_a, V, "classes_a"), _class_lists(classes_b, V, "classes_b")
+    cls_a, cls_b = _lists(classes_a, V, "classes_a", PARTS_MAX), _lists(classes_b, V, "classes_b", PARTS_MAX)
     n_a, n_b = [int(c.shape[0]) for c in cls_a], [int(c.shape[0]) for c in cls_b]
     # ---- 1. back-projection ----
-    if dev.type == "cuda":
-        hip = _need_hip("articulation_from_maps")
-        Kd = Kc.to(dev, non_blocking=True)
-        (rows_a, valid_a, _), (rows_b, valid_b, _) = (hip.frame_backproject(d, c, Kd, None, depth_scale, flip)
-                                                      for d, c in ((da, rgb_a), (db, rgb_b)))
-    else:
-        back = []
-        for d, c in ((da, rgb_a), (db, rgb_b)):
-            d = d.numpy()
-            rows, valid = inference._backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, c.numpy(), Kc.numpy(), None,
-                                                       depth_scale, flip)
-            back.append((torch.from_numpy(rows), torch.from_numpy(valid.reshape(V, H, W).astype(np.uint8))))
-        (rows_a, valid_a), (rows_b, valid_b) = back
+    hip = _need_hip("articulation_from_maps") if dev.type == "cuda" else None
+    (rows_a, valid_a, _), (rows_b, valid_b, _) = (inference.backproject_frames(d, None, Kc, None, depth_scale, flip) for d in (da, db))
     # ---- 2 + 3. overlap, match, the one host read ----
     match_ab, m_inter, m_union, area_a, area_b, ca, _ = _match_tables(inst_a, valid_a, cls_a, inst_b, valid_b, cls_b, float(min_iou))
     matches = _part_matches(match_ab, m_inter, m_union, area_a, area_b, n_a, n_b)
@@ -340,8 +296,7 @@ def articulation_from_frames(predictor, depth_a, rgb_a, depth_b, rgb_b, K, presa
     """``predictor.predict_frames`` on both frames (``presample``, ``seed``, ``isolate``, ``depth_scale``, ``flip`` and ``frame_picks``
     - its ``picks`` - go to it; ``sampler``: another sampler than the predictor's), then ``articulation_from_maps`` on their
     ``instance`` maps and ``proposal_classes`` (``kw``).  -> (frames_a, frames_b, articulation)"""
-    if sampler is not None and sampler != predictor.sampler:
-        predictor = type(predictor)(predictor.model, num_points=predictor.num_points, max_iters=predictor.max_iters, sampler=sampler)
+    predictor = predictor.with_sampler(sampler)
     shared = dict(picks=frame_picks, presample=presample, seed=seed, depth_scale=depth_scale, flip=flip, isolate=isolate)
     frames_a = predictor.predict_frames(depth_a, rgb_a, K, **shared)
     frames_b = predictor.predict_frames(depth_b, rgb_b, K, **shared)

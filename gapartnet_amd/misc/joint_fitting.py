@@ -89,6 +89,33 @@ def _need_hip(what: str):
     return hip
 
 
+def _maps(inst, what: str) -> torch.Tensor:
+    """[V,H,W] (or [H,W], or a sequence of [H,W]) integer tensor"""
+    if not torch.is_tensor(inst) and len(inst) > 0 and torch.is_tensor(inst[0]):
+        inst = torch.stack(list(inst))
+    inst = torch.as_tensor(inst)
+    if inst.dim() == 2:
+        inst = inst[None]
+    if inst.dim() != 3 or inst.dtype.is_floating_point or inst.dtype == torch.bool:
+        raise ValueError(f"{what} must be an integer [V,H,W] (or [H,W]) map")
+    return inst
+
+
+def _lists(values, V: int, what: str, cap: Optional[int] = None) -> list:
+    """one 1-D tensor per frame (class lists, scores); a single frame may pass its list bare.  ``cap``: the longest list allowed"""
+    if torch.is_tensor(values) or isinstance(values, np.ndarray):
+        values = [values] if values.ndim == 1 else list(values)
+    values = list(values)
+    if V == 1 and all(np.ndim(c) == 0 for c in values):  # (a flat list of values, the empty one included)
+        values = [values]
+    if len(values) != V:
+        raise ValueError(f"{what}: {V} frames need {V} lists, got {len(values)}")
+    out = [c.reshape(-1) if torch.is_tensor(c) else torch.as_tensor(np.asarray(c).reshape(-1)) for c in values]
+    if cap is not None and any(int(c.shape[0]) > cap for c in out):
+        raise ValueError(f"{what}: at most {cap} parts a frame, got {max(int(c.shape[0]) for c in out)}")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------ sampling
 def _joint_sample_torch(pc1s, pc2s, picks1, picks2, k1, k2):
     B, K = picks1.shape
@@ -331,22 +358,10 @@ def joints_from_frames(depth_a, depth_b, K, mask_a, mask_b, depth_scale: float =
     from .. import inference
     sides = []
     for depth, mask in ((depth_a, mask_a), (depth_b, mask_b)):
-        depth = torch.as_tensor(depth)
-        rgb = torch.zeros(tuple(depth.shape) + (3,), dtype=torch.uint8, device=depth.device)  # (the frame path takes colours along)
-        depth, rgb, Kc, keep = inference._check_frames(depth, rgb, K, torch.as_tensor(mask))
+        depth, _, Kc, keep = inference._check_frames(depth, None, K, torch.as_tensor(mask))
         V, H, W = (int(v) for v in depth.shape)
-        if depth.is_cuda:
-            hip = _need_hip("joints_from_frames")
-            rows, valid, counts = hip.frame_backproject(depth, rgb, Kc.to(depth.device, non_blocking=True), keep.to(depth.device),
-                                                        depth_scale, flip)
-            valid = valid.reshape(V, H * W).bool()
-        else:
-            d = depth.numpy()
-            rows, valid = inference._backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), Kc.numpy(),
-                                                       keep.numpy(), depth_scale, flip)
-            rows, valid = torch.from_numpy(rows), torch.from_numpy(valid)
-            counts = valid.sum(1)
-        sides.append((rows[:, :3].reshape(V, H * W, 3), valid, counts))
+        rows, valid, counts = inference.backproject_frames(depth, None, Kc, keep.to(depth.device), depth_scale, flip)
+        sides.append((rows[:, :3].reshape(V, H * W, 3), valid.reshape(V, H * W).bool(), counts))
     counts = torch.cat([s[2] for s in sides]).tolist()          # the one host read
     clouds = []
     for xyz, valid, _ in sides:

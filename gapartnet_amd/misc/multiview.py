@@ -36,7 +36,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from .joint_fitting import _need_hip
+from .joint_fitting import _lists, _maps, _need_hip
 from .pose_fitting_batched import draw_picks, estimate_pose_from_npcs_batched
 
 VIEWS_MAX = 64        # GPN_VIEWS_MAX
@@ -224,29 +224,6 @@ def _gather_numpy(wrows, npcs, fused_inst, seg_start, n_total: int):
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
-def _maps(inst, what: str) -> torch.Tensor:
-    if not torch.is_tensor(inst) and len(inst) > 0 and torch.is_tensor(inst[0]):
-        inst = torch.stack(list(inst))
-    inst = torch.as_tensor(inst)
-    if inst.dim() == 2:
-        inst = inst[None]
-    if inst.dim() != 3 or inst.dtype.is_floating_point or inst.dtype == torch.bool:
-        raise ValueError(f"{what} must be an integer [V,H,W] (or [H,W]) map")
-    return inst
-
-
-def _lists(values, V: int, what: str) -> list:
-    """one 1-D tensor per view; a single view may pass its list bare"""
-    if torch.is_tensor(values) or isinstance(values, np.ndarray):
-        values = [values] if values.ndim == 1 else list(values)
-    values = list(values)
-    if V == 1 and all(np.ndim(c) == 0 for c in values):
-        values = [values]
-    if len(values) != V:
-        raise ValueError(f"{what}: {V} views need {V} lists, got {len(values)}")
-    return [c.reshape(-1) if torch.is_tensor(c) else torch.as_tensor(np.asarray(c).reshape(-1)) for c in values]
-
-
 def _poses(R, t, V: int):
     R = torch.as_tensor(np.asarray(R, dtype=np.float64) if not torch.is_tensor(R) else R).detach().cpu().double().reshape(-1, 3, 3)
     t = torch.as_tensor(np.asarray(t, dtype=np.float64) if not torch.is_tensor(t) else t).detach().cpu().double().reshape(-1, 3)
@@ -278,9 +255,7 @@ def fuse_parts(depth, K, inst, classes, R, t, npcs=None, scores=None, depth_scal
     ``min_inter``, ``min_overlap``: the rules of include/gpn.h section MV - their defaults are NOT tuned on real data.  On the GPU:
     ONE host read (the small tables) in front of the fit."""
     from .. import inference
-    depth = torch.as_tensor(depth)
-    rgb = torch.zeros(tuple(depth.shape) + (3,), dtype=torch.uint8, device=depth.device)  # (the frame path takes colours along)
-    depth, rgb, Kc, keep = inference._check_frames(depth, rgb, K, keep)
+    depth, _, Kc, keep = inference._check_frames(depth, None, K, keep)
     inst = _maps(inst, "inst")
     if depth.shape != inst.shape or depth.device != inst.device:
         raise ValueError("the depth frames and instance maps have one shape and live on one device")
@@ -310,9 +285,9 @@ def fuse_parts(depth, K, inst, classes, R, t, npcs=None, scores=None, depth_scal
             raise ValueError(f"npcs must be [{V},{H},{W},3] on the frames' device")
         npcs = npcs.to(torch.float32).contiguous()
     # ---- 1 - 4. world rows, occupancy, merge, relabel; the one host read ----
+    hip = _need_hip("fuse_parts") if dev.type == "cuda" else None
+    rows, valid, _ = inference.backproject_frames(depth, None, Kc, keep, depth_scale, False)
     if dev.type == "cuda":
-        hip = _need_hip("fuse_parts")
-        rows, valid, _ = hip.frame_backproject(depth, rgb, Kc.to(dev, non_blocking=True), keep, depth_scale, False)
         wrows, part_of, area, lo = hip.views_world(rows, valid, inst, n_parts, Rc.to(dev, non_blocking=True), tc.to(dev, non_blocking=True), GT)
         vol, inter, dropped = hip.views_overlap(wrows, part_of, lo, cell, GT)
         m = hip.views_merge(inter, vol, cls_all, n_parts, min_inter, min_overlap)
@@ -326,10 +301,7 @@ def fuse_parts(depth, K, inst, classes, R, t, npcs=None, scores=None, depth_scal
         m = dict(fused_of=parts[2], n_fused=parts[3], fused_class=parts[4], fused_vol=parts[5], fused_parts=parts[6].reshape(GT, V),
                  links=parts[7].reshape(GT, 3), n_links=parts[8], fused_views=np.ascontiguousarray(parts[9]).view(np.uint64))
     else:
-        d = depth.numpy()
-        rows, valid = inference._backproject_numpy(d.view(np.uint16) if d.dtype == np.int16 else d, rgb.numpy(), Kc.numpy(),
-                                                   None if keep is None else keep.numpy(), depth_scale, False)
-        wrows, part_of, area, lo = _world_numpy(rows, valid.reshape(V, H, W), inst.numpy(), n_parts, Rc.numpy(), tc.numpy(), GT)
+        wrows, part_of, area, lo = _world_numpy(rows.numpy(), valid.numpy(), inst.numpy(), n_parts, Rc.numpy(), tc.numpy(), GT)
         keys, dropped = _keys_numpy(wrows, part_of, lo, float(cell), GT)
         vol, inter = _tables_numpy(keys, GT)
         m = _merge_numpy(inter, vol, cls_all.numpy(), n_parts, int(min_inter), float(min_overlap))
@@ -385,8 +357,7 @@ def fuse_frames(predictor, depth, rgb, K, R, t, presample: int = 4, seed=0, isol
     """``predictor.predict_frames`` on all views (``presample``, ``seed``, ``isolate``, ``depth_scale`` and ``frame_picks`` - its
     ``picks`` - go to it; ``sampler``: another sampler than the predictor's), then ``fuse_parts`` on their ``instance`` maps,
     ``proposal_classes``, ``proposal_scores`` and ``npcs`` (``kw``).  -> (frames, fused)"""
-    if sampler is not None and sampler != predictor.sampler:
-        predictor = type(predictor)(predictor.model, num_points=predictor.num_points, max_iters=predictor.max_iters, sampler=sampler)
+    predictor = predictor.with_sampler(sampler)
     frames = predictor.predict_frames(depth, rgb, K, picks=frame_picks, presample=presample, seed=seed, depth_scale=depth_scale,
                                       flip=False, isolate=isolate)
     fused = fuse_parts(depth, K, torch.stack([f.instance for f in frames]), [f.proposal_classes for f in frames], R, t,

@@ -171,7 +171,34 @@ def test_null_classes_mean_all_classes_equal(cuda):
     assert np.array_equal(got["match_ab"][0], ab)
 
 
-@pytest.mark.parametrize("name", ["1x1", "1x64", "1x65", "32x32", "25x41", "512x514", "parts 63 and 64", "ragged batch", "every bin 1"])
+def test_match_when_only_the_index_breaks_the_ties(cuda):
+    """gpn_parts_match on a 64 x 64 table whose pairs all have the same inter and whose parts all have the same area: one IoU for
+    all 4096 candidates, so each round's arg-max is decided by the tie rule alone (the smaller (i, j)), in the lanes and across waves"""
+    _C, L, _stream = _lib()
+    P = 64
+    inter, area = np.full((P, P), 5, np.int32), np.full(P, 10, np.int32)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(cuda)  # noqa: E731
+    it, aa, ab, n = t(inter[None]), t(area[None]), t(area[None]), t([P])
+    bufs = {k: Guarded(shape, torch.int32, cuda) for k, shape in dict(match_ab=(1, P), match_ba=(1, P), n_matched=(1,), m_inter=(1, P),
+                                                                     m_union=(1, P)).items()}
+    p = lambda name: _C.ptr(bufs[name].t)  # noqa: E731
+    _C.check(L.gpn_parts_match(_C.ptr(it), _C.ptr(aa), _C.ptr(ab), _C.ptr(n), _C.ptr(n), _C.ptr(None), _C.ptr(None), ctypes.c_double(MIN_IOU),
+                               _C.i32(1), _C.i32(P), _C.i32(P), p("match_ab"), p("match_ba"), p("n_matched"), p("m_inter"), p("m_union"),
+                               _stream()), "gpn_parts_match")
+    torch.cuda.synchronize()
+    for name, b in bufs.items():
+        b.check(name)
+    got = {k: b.t.cpu().numpy() for k, b in bufs.items()}
+    areas = {i: 10 for i in range(P)}
+    taken = REF.match({(i, j): 5 for i in range(P) for j in range(P)}, areas, areas, None, None, MIN_IOU)
+    ab_, ba_, n_, mi, mu = REF.match_tables(taken, P, P)
+    assert n_ == P and np.array_equal(ab_, np.arange(P)), "the restatement matches (i, i), in that order"
+    assert np.array_equal(got["match_ab"][0], ab_) and np.array_equal(got["match_ba"][0], ba_) and got["n_matched"][0] == n_
+    assert np.array_equal(got["m_inter"][0], mi) and np.array_equal(got["m_union"][0], mu)
+
+
+@pytest.mark.parametrize("name", ["1x1", "1x64", "1x65", "32x32", "25x41", "512x514", "parts 63 and 64", "parts 64 and 64", "ragged batch",
+                                  "every bin 1"])
 def test_gather_equals_the_restatement(cuda, name):
     """segments in an order that is not the part order, some parts dropped (seg_start = -1), parts of 0 and 1 pixels among them, a gap
     before the first segment and one behind the last: every row of pc outside the segments keeps its sentinel"""

@@ -340,6 +340,58 @@ def test_merge_on_random_tables(cuda, GT, V):
         assert int(want["n_links"][0]) > 0
 
 
+def test_merge_when_only_the_index_breaks_the_ties(cuda):
+    """every pair of the table has the same inter and every part the same volume: one ratio for all candidates, so each round's
+    arg-max is decided by the tie rule alone (the smaller (g, h)), in the lanes, across the 16 waves - 130 rows put candidates
+    in every wave - and against the empty candidate of a thread without one"""
+    GT, V = 130, 64
+    n_parts = [3, 3] + [2] * 62
+    assert sum(n_parts) == GT
+    vol = np.full(GT, 6, np.int32)
+    inter = np.full((GT, GT), 3, np.int32)
+    np.fill_diagonal(inter, 0)
+    got = run_merge(cuda, inter, vol, None, n_parts, 1, 0.25)
+    want = REF.merge(inter, vol, None, n_parts, 1, 0.25)
+    for k in MERGE_OUT:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    links = want["links"][:int(want["n_links"][0])]
+    assert len(links) > 60 and (links[:, 2] == 3).all() and (links[0, :2] == (0, 3)).all()
+
+
+# ---- gather at more than 256 fused parts --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_npcs", [False, True])
+@pytest.mark.parametrize("V,H,W,F", [(2, 1, 1030, 300), (3, 5, 411, 512)])
+def test_gather_of_more_than_256_fused_parts_over_several_chunks(cuda, V, H, W, F, with_npcs):
+    """gpn_views_gather on a synthetic map (no merge behind it): more fused parts than the workgroup has threads, so the slot table
+    is walked in more than one step, and pixel noise, so a wave ballots over many distinct 9-bit keys; more than one chunk a view.
+    Keys run over -1 .. F (F itself is no part) with INT32_MIN among them, every part occurs; segments in a shuffled order, every
+    fifth part dropped, padding rows in front and behind"""
+    rng = np.random.RandomState(F)
+    N = V * H * W
+    assert F > 256 and H * W > 1024
+    fused = rng.randint(-1, F + 1, N).astype(np.int64)
+    at = rng.permutation(N)
+    fused[at[:F]] = np.arange(F)
+    fused[at[F:F + N // 50]] = INT32_MIN
+    fused = fused.astype(np.int32).reshape(V, H, W)
+    count = np.bincount(fused[(fused >= 0) & (fused < F)], minlength=F)
+    assert (count > 0).all() and (fused == F).any() and (fused == -1).any()
+    wrows = rng.standard_normal((N, 3)).astype(np.float32)
+    npcs = rng.uniform(size=(V, H, W, 3)).astype(np.float32) if with_npcs else None
+    seg, row = np.full(F, -1, np.int64), 2
+    for f in rng.permutation(F):
+        if f % 5 == 4:
+            continue
+        seg[f] = row
+        row += int(count[f])
+    n_total = row + 3
+    want = REF.gather(wrows, npcs, fused, seg.tolist(), n_total, FILL)
+    got = run_gather(cuda, wrows, npcs, fused, seg, n_total)
+    for g, x in zip(got, want):
+        np.testing.assert_array_equal(g, x)
+    assert (got[2][:2] == int(FILL)).all() and (got[2][-3:] == int(FILL)).all() and (got[2][2:-3] >= 0).all()
+
+
 # ---- argument errors and empty calls -------------------------------------------------------------------------------------------------------
 def test_argument_errors_and_empty_calls(cuda):
     _C, L, _stream = _lib()
